@@ -11,7 +11,9 @@ coordinate): zero_grad, SPVCNN forward (kernel maps rebuilt every step, as the r
 augmentation forces), cross-entropy(ignore 255), backward, Adam step -- conv operands bf16 with
 f32 accumulation (BASELINE.json configs[1]).  value = input voxels of all ranks / second.
 
-One JSON line is printed by rank 0.  Besides the contract fields it carries
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times the steps and prints the contract fields
+(metric, value, unit, ms_per_step, ...); --dump-outputs DIR also writes what the last timed step computed (see
+dump_outputs).  With --full the line carries besides them
   roofline      the dominant kernel (fused sparse conv, the level-0 96->96 k3 layer) timed live
                 with HIP events on the launch stream: algorithmic bytes / duration
   families      one more (untimed) step with every library call bracketed by events: GPU time,
@@ -78,6 +80,11 @@ def parse():
     ap.add_argument('--roofline-only', action='store_true',
                     help='only the dominant-kernel measurement (for rocprofv3: every launch of the '
                          'kernel in the trace is then the roofline layer)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the extras of the line (host, roofline, families, variants, secondary, CPU baselines); '
+                         'the --no-* switches above select among them')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32)')
     return ap.parse_args()
 
 
@@ -217,16 +224,41 @@ def bench_train(world, rank, dev, model_name, dtype, batch, steps, warmup, ddp=T
     first = count[0]
     t0 = time.perf_counter()
     for _ in range(steps):
-        loss, _ = step()
+        outputs = step()
     t_host = time.perf_counter() - t0           # the host has queued every step (it runs ahead of the GPU unless it is the bound)
     barrier_sync(world if ddp else 1)
     dt = time.perf_counter() - t0
     if ddp:
         dt = max_over_ranks(dt, world, dev)
+    loss = outputs[0]
     assert np.isfinite(loss.item()), 'training diverged'
     voxels = sum(int(batches[(first + i) % len(batches)][0].shape[0]) for i in range(steps)) / steps
     return {'model': model, 'step': step, 'seconds': dt, 'steps': steps, 'voxels': voxels,
-            'loss': float(loss.item()), 'host_seconds': t_host}
+            'loss': float(loss.item()), 'host_seconds': t_host, 'outputs': outputs}
+
+
+DUMP_BUDGET = 60 * 10 ** 6               # bytes of --dump-outputs in all (the limit is 64 MB)
+DUMP_PARAMS = 1 << 20                   # parameters sampled after the last Adam step
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: what the last timed step handed its caller -- train_step's loss and logits -- and a fixed sample
+    of the parameters its Adam step left, as float32 DIR/<name>.npy.  The batch and the initial weights are seeded, so
+    two builds run with the same arguments can be compared file by file.  Logits past the budget are cut to a fixed,
+    seeded sample of rows."""
+    os.makedirs(path, exist_ok=True)
+    loss, logits = res['outputs']
+    params = torch.cat([p.detach().reshape(-1).float() for p in res['model'].parameters()]).cpu()
+    g = torch.Generator().manual_seed(7122)
+    pick = torch.randperm(params.numel(), generator=g)[:DUMP_PARAMS].sort().values
+    arrays = {'loss': loss.float().reshape(1).cpu(), 'params_sample': params[pick]}
+    logits = logits.float().cpu()
+    room = (DUMP_BUDGET - sum(a.numel() * 4 for a in arrays.values())) // (4 * logits.shape[1])
+    if logits.shape[0] > room:
+        logits = logits[torch.randperm(logits.shape[0], generator=g)[:room].sort().values]
+    arrays['logits'] = logits
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a.numpy().astype(np.float32))
 
 
 def host_calls(model_name, dtype, batch, dev, prefetch=True):
@@ -1283,6 +1315,8 @@ def main():
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     solo = rank == 0 and world == 1         # the extras describe one GPU; N>1 runs report the contract line
+    if not args.full:                       # a plain run: the headline only
+        args.no_cpu_baseline = args.no_secondary = args.no_roofline = args.no_families = args.no_variants = True
     # ---- host-only work first: process pools (input generation, the CPU baselines) start their
     #      workers BEFORE this process touches the GPU (a GPU-initialised process must not exec)
     frames = batches = None
@@ -1314,6 +1348,8 @@ def main():
         return
     res = bench_train(world, rank, dev, args.model, args.dtype, batch, args.steps, args.warmup)
     log('train timed: %.3f s for %d steps' % (res['seconds'], args.steps))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
     ms = res['seconds'] / args.steps * 1e3
     voxels = sum_over_ranks(float(res['voxels']), world, dev)
     line = {
@@ -1331,7 +1367,7 @@ def main():
                    'voxels_per_step_per_gpu': int(voxels / world),
                    'parallelism': 'dp%d' % world, 'loss': round(res['loss'], 4)},
     }
-    if solo:
+    if solo and args.full:
         line['host'] = guarded(host_calls, args.model, args.dtype, batch, dev)
         if isinstance(line['host'], dict):
             # wall time the host needed to QUEUE the timed steps (no synchronisation inside).  Well under ms_per_step: the

@@ -7,7 +7,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out/final6_$TAG; mkdir -p $O
 B="python3 $GRAFT_REPO_ROOT/bench.py"
 QUIET="--no-cpu-baseline --no-secondary --no-roofline --no-families --no-variants"
 cd $GRAFT_REPO_ROOT
-timeout 1800 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; tail -2 $O/bench.err | cut -c1-200; head -c 300 $O/bench_line.json; echo
+timeout 1800 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; tail -2 $O/bench.err | cut -c1-200; head -c 300 $O/bench_line.json; echo
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/step -- $B --steps 7 --warmup 3 $QUIET > $O/step.log 2>&1; echo "step rc=$?"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/roof -- $B --roofline-only > $O/roof.log 2>&1; echo "roof rc=$?"

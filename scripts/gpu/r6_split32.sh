@@ -14,7 +14,7 @@ for form in 16 32; do
 done
 for form in 16 32; do
   echo "=== LIDAL_SPLIT_MFMA=$form, f32 frames/s"
-  BENCH_SECONDARY_F32_ONLY=1 LIDAL_SPLIT_MFMA=$form timeout 900 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-families --no-variants > $O/bench_$form.json 2> $O/bench_$form.err
+  BENCH_SECONDARY_F32_ONLY=1 LIDAL_SPLIT_MFMA=$form timeout 900 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-families --no-variants > $O/bench_$form.json 2> $O/bench_$form.err
   python3 -c "import json,sys; d=json.load(open('$O/bench_$form.json')); print(d['ms_per_step'], json.dumps(d['secondary']['by_nei']))"
 done
 timeout 1200 python -m pytest tests/test_teacher_forced_gpu.py tests/test_scoring_gpu.py tests/test_plan_gpu.py -x -q -m gpu 2>&1 | tail -5

@@ -19,7 +19,7 @@ cat $O/summary_16.txt $O/summary_32.txt | grep -v "^==" | sort | head -150
 cat $O/stats_16.csv $O/stats_32.csv
 cd $GRAFT_REPO_ROOT
 timeout 600 python -m pytest tests/test_scoring_gpu.py -x -q -m gpu -k "256" 2>&1 | tail -5
-timeout 1500 python bench.py --steps 10 --warmup 3 --no-families > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -3 $O/bench.err
+timeout 1500 python bench.py --full --steps 10 --warmup 3 --no-families > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -3 $O/bench.err
 python3 -c "
 import json; d=json.load(open('$O/bench.json')); s=d['secondary']
 print(d['ms_per_step'], s.get('value'), json.dumps(s.get('roofline')), json.dumps(s['by_dtype'].get('f32_exact')), json.dumps(s['by_dtype']['bf16'].get('roofline')))

@@ -11,8 +11,8 @@ for rep in 1 2; do
 import json; d=json.load(open('$O/b_${rows}_$rep.json')); print('rows>=$rows rep $rep: ms_per_step', d['ms_per_step'], 'value', d['value'])"
   done
 done
-LIDAL_WGRAD_STREAMS_ROWS=0 timeout 900 python bench.py --steps 10 --warmup 4 --no-cpu-baseline --no-secondary --no-roofline --no-variants > $O/fam_off.json 2>$O/fam_off.err
-timeout 900 python bench.py --steps 10 --warmup 4 --no-cpu-baseline --no-secondary --no-roofline --no-variants > $O/fam_on.json 2>$O/fam_on.err
+LIDAL_WGRAD_STREAMS_ROWS=0 timeout 900 python bench.py --full --steps 10 --warmup 4 --no-cpu-baseline --no-secondary --no-roofline --no-variants > $O/fam_off.json 2>$O/fam_off.err
+timeout 900 python bench.py --full --steps 10 --warmup 4 --no-cpu-baseline --no-secondary --no-roofline --no-variants > $O/fam_on.json 2>$O/fam_on.err
 python3 -c "
 import json
 for t in ('off','on'):

@@ -83,7 +83,7 @@ def test_bench_prints_exactly_one_json_line_with_the_contract_keys():
     env = dict(os.environ, BENCH_FORCE_DDP='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK='0', WORLD_SIZE='1',
                LOCAL_RANK='0')              # (one rank over RCCL: its version banner must not reach stdout)
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
-                          '--no-cpu-baseline', '--no-variants', '--no-families', '--no-secondary'],
+                          '--full', '--no-cpu-baseline', '--no-variants', '--no-families', '--no-secondary'],
                          capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -104,6 +104,37 @@ def test_bench_prints_exactly_one_json_line_with_the_contract_keys():
         assert r['traffic'] > r['algorithmic_bytes_per_launch'] and r['traffic_source'].startswith('offline PMC passes')
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """Without --full the line is the headline alone (no extras are measured), and --dump-outputs writes what the last
+    timed step computed -- its loss, its logits, a sample of the parameters after its Adam step -- as float32, within
+    64 MB, from seeded inputs: two runs with the same arguments compute on the same batch and the same weights."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+                          '--frames', '1', '--points', '30000', '--dump-outputs', str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in d, k
+    assert d['steps'] == 2 and d['value'] > 0 and d['ms_per_step'] > 0
+    for k in ('host', 'roofline', 'families', 'variants', 'secondary', 'cpu_baseline'):
+        assert k not in d, k
+    files = sorted(os.listdir(tmp_path))
+    assert files == ['logits.npy', 'loss.npy', 'params_sample.npy'], files
+    arr = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arr.values())
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in files) <= 64 * 10 ** 6
+    assert arr['logits'].shape == (d['config']['voxels_per_step_per_gpu'], 19)
+    assert abs(float(arr['loss'][0]) - d['config']['loss']) < 1e-3
+
+
 def test_bench_starts_its_own_ranks_when_no_launcher_did():
     """`python bench.py --gpus 2` from a plain shell (no WORLD_SIZE in the environment): the parent starts two fresh rank
     processes before touching the GPU (as train.py:163-203 / prob_inference.py:219-223 mp.spawn theirs), relays rank 0's
@@ -116,7 +147,7 @@ def test_bench_starts_its_own_ranks_when_no_launcher_did():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env.update(BENCH_SINGLE_DEVICE='1', BENCH_BACKEND='gloo', BENCH_LAUNCH_TIMEOUT='900')
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                          '--no-cpu-baseline', '--score-frames', '7', '--nei', '10', '--points', '30000'],
+                          '--full', '--no-cpu-baseline', '--score-frames', '7', '--nei', '10', '--points', '30000'],
                          capture_output=True, text=True, timeout=1200, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
