@@ -558,6 +558,34 @@ int lidal_supervoxel_reduce(const double* interd, const float* intere, const dou
                             const int64_t* sv_ptr, const int64_t* sv_idx, int s, float* sv_interd,
                             float* sv_intere, float* sv_center, void* stream);
 
+/* ---- ReDAL region selection (score/sv_level/ReDAL.py, dataset/ReDAL/gen_surface_variation_sk.py; csrc/redal.hip) ---- */
+/* k nearest OTHER points of every point of a raw scan xyz f32 [p,3]: knn i32 [p,k], sorted by (f64 distance, index).
+ * 1 <= k <= 64; p < k + 1 is refused (status 2, lidal_last_error).  `cell`: the search grid's cell in metres (the
+ * result does not depend on it).  Workspace: lidal_knn_workspace_bytes(p). */
+int64_t lidal_knn_workspace_bytes(int64_t p);
+int lidal_knn(const float* xyz, int64_t p, int k, double cell, int32_t* knn, void* ws, int64_t ws_bytes, void* stream);
+/* surface variation of every point: lambda_min / (lambda_1 + lambda_2 + lambda_3) of the population covariance of its
+ * k nearest other points (f64, Jacobi eigenvalues), clipped at `threshold`: sigma f32 [p].  Same workspace. */
+int lidal_surface_variation(const float* xyz, int64_t p, int k, double cell, float threshold, float* sigma, void* ws,
+                            int64_t ws_bytes, void* stream);
+/* ReDAL.py:59-74 for one frame: point_score = alpha * mean_c(-prob * log2(prob + 1e-12)) + gamma * curvature, then per
+ * supervoxel s of the CSR (sv_ptr i64 [s+1], sv_idx i64): sv_scores f32 [s] (mean point_score), sv_feats f32 [s,d]
+ * (mean feature row), sv_pnums i64 [s].  prob f32 [p,c] (c <= 32), feat f32 [p,d], curvature f32 [p].
+ * Workspace: lidal_region_scores_workspace_bytes(p). */
+int64_t lidal_region_scores_workspace_bytes(int64_t p);
+int lidal_region_scores(const float* prob, int64_t p, int c, const float* feat, int d, const float* curvature,
+                        const int64_t* sv_ptr, const int64_t* sv_idx, int s, float alpha, float gamma, float* sv_scores,
+                        float* sv_feats, int64_t* sv_pnums, void* ws, int64_t ws_bytes, void* stream);
+/* One k-means run: greedy k-means++ seeding from row `first` with the host-drawn uniforms
+ * u f64 [(k-1) * trials] (device), then up to max_iter Lloyd iterations (stop: labels unchanged, or the summed squared
+ * centre shift <= tol), then a final assignment.  x f32 [n,d] (d <= 128).  Out: seeds i32 [k], labels i32 [n],
+ * centers f64 [k,d] (device); *inertia_host, *n_iter_host (host).  Synchronises the stream once per iteration.
+ * Workspace: lidal_kmeans_workspace_bytes(n, d, k, trials). */
+int64_t lidal_kmeans_workspace_bytes(int64_t n, int d, int k, int trials);
+int lidal_kmeans(const float* x, int64_t n, int d, int k, int64_t first, const double* u, int trials, int max_iter,
+                 double tol, int32_t* seeds, int32_t* labels, double* centers, double* inertia_host,
+                 int32_t* n_iter_host, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- row-wise helpers of a planned step (what torch glue did between the operators) ------------- */
 /* dst[r][0 : row_bytes) = src[r][0 : row_bytes), dst[r][row_bytes : row_bytes + zero_bytes) = 0 for r < rows; rows
  * `src_pitch` / `dst_pitch` bytes apart.  One call per summand is torchsparse.cat (operators.py; network/spvcnn.py:

@@ -137,6 +137,15 @@ SIGNATURES = {
     'lidal_interframe_score_ordered': (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _f64, _vp,
                                               _vp, _vp, _vp, _i64, _vp, _vp]),
     'lidal_supervoxel_reduce': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    'lidal_knn_workspace_bytes': (_i64, [_i64]),
+    'lidal_knn': (_i32, [_vp, _i64, _i32, _f64, _vp, _vp, _i64, _vp]),
+    'lidal_surface_variation': (_i32, [_vp, _i64, _i32, _f64, _f32, _vp, _vp, _i64, _vp]),
+    'lidal_region_scores_workspace_bytes': (_i64, [_i64]),
+    'lidal_region_scores': (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp,
+                                   _i64, _vp]),
+    'lidal_kmeans_workspace_bytes': (_i64, [_i64, _i32, _i32, _i32]),
+    'lidal_kmeans': (_i32, [_vp, _i64, _i32, _i32, _i64, _vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                            _vp]),
     'lidal_copy2d': (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp]),
     'lidal_add2d': (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp]),
     'lidal_transpose_f32': (_i32, [_vp, _i64, _vp, _i32, _i32, _vp]),

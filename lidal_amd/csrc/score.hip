@@ -8,12 +8,14 @@
 
 
 #include "common.h"
+#include "grid.h"
 
 // The reference computes these quantities with numpy (separately rounded products and sums); hipcc
 // contracts a*b+c into fma even through __dmul_rn/__dadd_rn, so this unit is built with
 // -ffp-contract=off (lidal_amd/build.py).
 
 using namespace lidal;
+using namespace lidal::grid;
 
 namespace {
 
@@ -126,39 +128,6 @@ __global__ void __launch_bounds__(256) register_kernel(const float* __restrict__
 }
 
 // ---------------- uniform grid for radius-limited nearest neighbour ----------------
-// grid buffer: [header 64 B][table 12*cap][sorted_keys 8*p][sorted_idx 4*p]
-struct GridHeader {
-  int64_t p;
-  int64_t cap;
-  double cell;
-  double inv_cell_unused;
-};
-
-struct __attribute__((aligned(16))) GridRec { unsigned long long key; double x, y, z; int idx; int pad; };
-
-struct GridView {
-  TableView t;
-  const uint64_t* keys;
-  const int* idx;
-  const struct GridRec* rec;     // the points in cell order, one 48-byte record each (round 5: a candidate -- its cell key, its
-                                 // coordinates, its id -- is ONE access instead of three arrays and a gathered point)
-  int64_t p;
-  double cell;
-};
-// byte offsets inside a grid buffer (after the 64-byte header) for p points and capacity cap:
-//   keys u64 [cap] | vals i32 [cap] | sorted cell keys u64 [p] | sorted point ids i32 [p] | records GridRec [p] |
-//   occupancy bitmap u32 [cap / 4] (8 bits per slot, csrc/common.h: most probed cells are empty)
-__host__ __device__ inline int64_t grid_off_skeys(int64_t cap) { return cap * 12; }
-__host__ __device__ inline int64_t grid_off_sidx(int64_t cap, int64_t q) { return cap * 12 + ((8 * q + 255) / 256) * 256; }
-__host__ __device__ inline int64_t grid_off_spts(int64_t cap, int64_t q) { return grid_off_sidx(cap, q) + ((4 * q + 255) / 256) * 256; }
-__host__ __device__ inline int64_t grid_off_bits(int64_t cap, int64_t q) { return grid_off_spts(cap, q) + ((48 * q + 255) / 256) * 256; }
-
-constexpr int64_t kBias = 1 << 20;
-
-__device__ __forceinline__ uint64_t cell_key(int64_t ix, int64_t iy, int64_t iz) {
-  return ((uint64_t)(ix + kBias) << 42) | ((uint64_t)(iy + kBias) << 21) | (uint64_t)(iz + kBias);
-}
-
 static inline int64_t grid_cap(int64_t p) { return table_capacity(p); }
 
 static inline GridView grid_view(const void* grid, int64_t p, int64_t cap, double cell) {

@@ -10,6 +10,8 @@ vice versa.
   sv_flag/.../<frame>.npy      i64 [S] in {0,1,2}   LiDAL.py:328-330
   super_voxel/KMeans/sv_pnums.npy, sv_centers.npy   i64 [sum S]; f32 [sum S, 3] with the
                                +1000 * sequence-index offset      LiDAL.py:173-177,220-222
+  boundary/<seq>/<frame>.npy   f32 [P]       the surface variation of a raw scan
+                               dataset/ReDAL/gen_surface_variation_sk.py -> ReDAL.py:57
   <dir>/current.pt             {'model_state_dict', 'iteration', 'ep_id'}   train.py:151-155
 """
 import os
@@ -19,7 +21,7 @@ import numpy as np
 import torch
 
 __all__ = ['save_prob_pred', 'load_prob', 'load_supervoxels', 'save_supervoxels', 'load_sv_flag',
-           'save_sv_flag', 'load_sv_stats', 'save_sv_stats', 'save_checkpoint', 'load_checkpoint']
+           'save_sv_flag', 'load_sv_stats', 'save_sv_stats', 'load_curvature', 'save_curvature', 'save_checkpoint', 'load_checkpoint']
 
 
 def _mkdir_for(path):
@@ -79,6 +81,21 @@ def save_sv_stats(pnums_path, centers_path, sv_pnums, sv_centers):
     _mkdir_for(pnums_path), _mkdir_for(centers_path)
     np.save(pnums_path, np.asarray(sv_pnums))
     np.save(centers_path, np.asarray(sv_centers))
+
+
+def load_curvature(path):
+    """boundary/<seq>/<frame>.npy -> f32 [P], read as ReDAL.py:57 reads it (`.astype(np.float32)`)."""
+    curv = np.load(path).astype(np.float32)
+    assert curv.ndim == 1, curv.shape
+    return curv
+
+
+def save_curvature(path, curvature):
+    """f32 [P] (a tensor or an array: score.surface_variation's output) -> boundary/<seq>/<frame>.npy, the file
+    gen_surface_variation_sk.py writes."""
+    curvature = curvature.detach().cpu().numpy() if torch.is_tensor(curvature) else np.asarray(curvature)
+    _mkdir_for(path)
+    np.save(path, curvature.astype(np.float32, copy=False))
 
 
 def save_checkpoint(directory, model, iteration, ep_id):

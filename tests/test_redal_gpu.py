@@ -1,0 +1,203 @@
+"""ReDAL region selection on the GPU (csrc/redal.hip through lidal_amd.score.redal) against the reference's worker_func,
+a scipy/numpy surface-variation restatement, scikit-learn's KMeans and this project's numpy restatement of its k-means
+definition (tests/redal_ref.py).  Fixtures: tests/golden/make_golden_redal.py."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import redal_inputs as RI
+import redal_ref
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+SCORE_ULPS = 4          # sv_scores: the one step not restated is numpy's f32 log2
+
+
+def _small(golden_dir):
+    return np.load(os.path.join(golden_dir, 'redal_small.npz'))
+
+
+def _sv(golden_dir):
+    return np.load(os.path.join(golden_dir, 'redal_sv.npz'))
+
+
+def test_knn_equals_kdtree_neighbours(golden_dir):
+    from lidal_amd.score import knn
+    g = _sv(golden_dir)
+    k = int(g['k'])
+    nb = knn(torch.from_numpy(g['xyz']).to(DEV), k).cpu().numpy()
+    assert nb.shape == (g['xyz'].shape[0], k)
+    checked = 0
+    for r, i in enumerate(g['sample']):
+        ids, dist = g['sample_knn'][r], g['sample_dist'][r]
+        if not g['own_first'][r] or dist[k] == dist[k + 1]:   # a duplicate of the point, or the k-th and (k+1)-th
+            continue                                            # other points tie: either may be in the list
+        assert set(nb[i].tolist()) == set(ids[1:k + 1].tolist()), i
+        checked += 1
+    assert checked >= 250
+    # sorted by distance
+    x = g['xyz'].astype(np.float64)
+    dd = ((x[nb[g['sample']]] - x[g['sample']][:, None]) ** 2).sum(-1)
+    assert (np.diff(dd, axis=1) >= 0).all()
+
+
+def test_surface_variation_matches_restatement(golden_dir):
+    from lidal_amd.score import surface_variation
+    g = _sv(golden_dir)
+    sig = surface_variation(torch.from_numpy(g['xyz']).to(DEV)).cpu().numpy()
+    ref = g['sigma']
+    err = np.abs(sig.astype(np.float64) - ref)
+    planar = g['sigma_raw'] < 0.01
+    print('surface variation: max |d sigma| %.3g (planar %.3g over %d points)' % (err.max(), err[planar].max(),
+                                                                                  planar.sum()))
+    assert planar.sum() > 1000
+    assert err.max() <= 1e-6
+    assert sig.max() <= np.float32(0.1)
+
+
+def test_surface_variation_refuses_too_few_points():
+    from lidal_amd.score import knn, surface_variation
+    xyz = torch.rand(50, 3, device=DEV)
+    with pytest.raises(RuntimeError, match='k \\+ 1'):
+        surface_variation(xyz)
+    with pytest.raises(RuntimeError, match='k \\+ 1'):
+        knn(xyz, 50)
+    assert surface_variation(torch.rand(51, 3, device=DEV)).shape == (51,)
+
+
+def test_region_scores_match_worker_func(golden_dir):
+    from lidal_amd.score import interframe, region_scores
+    g = _small(golden_dir)
+    frames = RI.worker_frames()
+    sc, ft, pn = [], [], []
+    for f in frames:
+        ptr, idx, _ = interframe.sv_csr(f['sv2point'], DEV)
+        s, fe, n = region_scores(torch.from_numpy(f['prob']).to(DEV), torch.from_numpy(f['outfeat']).to(DEV),
+                                 torch.from_numpy(f['curvature']).to(DEV), ptr, idx)
+        sc.append(s.cpu().numpy()), ft.append(fe.cpu().numpy()), pn.append(n.cpu().numpy())
+    sc, ft, pn = np.concatenate(sc), np.concatenate(ft), np.concatenate(pn)
+    assert np.array_equal(pn, g['worker_sv_pnums'])
+    assert np.array_equal(ft, g['worker_sv_feats'])                # sequential row sum: restated bit for bit
+    ref = g['worker_sv_scores']
+    ulps = np.abs(sc.view(np.int32).astype(np.int64) - ref.view(np.int32).astype(np.int64))
+    print('region scores: %d of %d bit-equal, max %d ulp' % ((ulps == 0).sum(), ulps.size, ulps.max()))
+    assert ulps.max() <= SCORE_ULPS
+
+
+def _seed0():
+    return int(np.random.RandomState(0).randint(2 ** 31 - 1, size=10)[0])
+
+
+def test_kmeans_seeds_and_one_step_equal_restatement():
+    from lidal_amd.score.redal import kmeans_single
+    x = RI.overlapping()[:3000]
+    s = _seed0()
+    xd = torch.from_numpy(x).to(DEV)
+    for it in (0, 1):
+        labels, centers, _, n_iter, seeds = kmeans_single(xd, 150, s, max_iter=it, tol=0.0)
+        r_labels, r_centers, r_it, r_seeds = redal_ref.kmeans_single(x, 150, s, max_iter=it)
+        assert np.array_equal(seeds.cpu().numpy(), r_seeds)
+        assert np.array_equal(labels.cpu().numpy(), r_labels)
+        assert np.array_equal(centers.cpu().numpy(), r_centers)
+        assert n_iter == r_it == it
+
+
+def test_kmeans_partitions_blobs_like_sklearn(golden_dir):
+    from lidal_amd.score import kmeans
+    g = _small(golden_dir)
+    labels, centers, inertia, _ = kmeans(RI.blobs(), n_clusters=150, random_state=0, n_init=10)
+    assert redal_ref.same_partition(labels, g['km_blobs_labels'])
+    print('blobs: inertia %.6g, sklearn %.6g' % (inertia, float(g['km_blobs_inertia'])))
+
+
+def test_kmeans_inertia_close_to_sklearn_on_overlapping_data(golden_dir):
+    from lidal_amd.score import kmeans
+    g = _small(golden_dir)
+    _, _, inertia, n_iter = kmeans(RI.overlapping(), n_clusters=150, random_state=0, n_init=10)
+    ratio = inertia / float(g['km_overlap_inertia'])
+    print('overlapping: inertia %.6g, sklearn (scikit-learn %s, best of 10) %.6g, ratio %.4f, %d iterations' % (
+        inertia, str(g['sklearn_version']), float(g['km_overlap_inertia']), ratio, n_iter))
+    assert ratio <= 1.02
+
+
+def test_kmeans_is_deterministic():
+    from lidal_amd.score.redal import kmeans_single
+    x = torch.from_numpy(RI.overlapping()).to(DEV)
+    a = kmeans_single(x, 150, 12345, max_iter=50)
+    b = kmeans_single(x, 150, 12345, max_iter=50)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and a[2] == b[2] and a[3] == b[3]
+
+
+def test_kmeans_relocates_empty_cluster():
+    """Ten copies of one row and two far rows, four clusters: D^2 is all zero after the far rows are taken, so the
+    fourth seed repeats a row, its cluster is empty after the first assignment, and it takes the farthest row (the lower
+    index on ties).  The device follows the restatement step by step."""
+    from lidal_amd.score.redal import kmeans_single
+    x = np.zeros((12, 8), np.float32)
+    x[10] = 100.0
+    x[11] = -100.0
+    xd = torch.from_numpy(x).to(DEV)
+    for it in (1, 2, 5):
+        labels, centers, inertia, n_iter, seeds = kmeans_single(xd, 4, 7, max_iter=it, tol=0.0)
+        r_labels, r_centers, r_it, r_seeds = redal_ref.kmeans_single(x, 4, 7, max_iter=it)
+        assert np.array_equal(seeds.cpu().numpy(), r_seeds)
+        assert len(np.unique(x[r_seeds], axis=0)) < 4   # two seeds on the same point: the case under test
+        assert np.array_equal(labels.cpu().numpy(), r_labels)
+        assert np.array_equal(centers.cpu().numpy(), r_centers)
+        assert n_iter == r_it and np.isfinite(inertia)
+
+
+def test_redal_sequence_board_and_selection():
+    """redal_sequence + RegionBoard + select_redal on a small synthetic sequence: the flags equal what the host
+    restatement (worker_func's reductions in numpy, the numpy k-means) computes from the same device intermediates
+    (probabilities, features, curvature)."""
+    from lidal_amd import synth
+    from lidal_amd.network import MinkUNet
+    from lidal_amd.score import RegionBoard, infer_frame, interframe, redal_sequence, select_redal, surface_variation
+    from weights import fill_state_dict
+    frames = synth.make_sequence(4, n_points=None, seed=21, step=0.5, n_beams=12, n_az=96, n_sv=20)
+    rng = np.random.default_rng(3)
+    model = fill_state_dict(MinkUNet(19)).eval().to(DEV)
+    dev_frames = []
+    for f in frames:
+        sb = synth.make_score_batch(f['points'], f['intensity'], rng, inf_reps=2)
+        ptr, idx, _ = interframe.sv_csr(f['sv2point'], DEV)
+        dev_frames.append({'coords': torch.from_numpy(sb['coords_v_b']).to(DEV),
+                           'feats': torch.from_numpy(sb['feats_v_b']).to(DEV),
+                           'inverse': torch.from_numpy(sb['inverse_indices_b']).to(DEV),
+                           'points': torch.from_numpy(f['points']).to(DEV), 'sv_ptr': ptr, 'sv_idx': idx})
+    out = redal_sequence(model, dev_frames, inf_reps=2)
+    n_sv = sum(len(f['sv_id']) for f in frames)
+    board = RegionBoard(n_sv)
+    board.add_sequence([f['sv_id'] for f in frames], out)
+    # host restatement from the device intermediates
+    scores = np.zeros(n_sv, np.float32)
+    feats = np.zeros((n_sv, RI.FT_DIM), np.float32)
+    pnums = np.zeros(n_sv, int)
+    for f, d in zip(frames, dev_frames):
+        prob, _, feat = infer_frame(model, d['coords'], d['feats'], d['inverse'], 2, return_feat=True)
+        curv = surface_variation(d['points']).cpu().numpy()
+        prob, feat = prob.cpu().numpy(), feat.cpu().numpy()
+        uncertain = np.mean(-prob * np.log2(prob + 1e-12), axis=1)
+        point_score = 1.0 * uncertain + 0.05 * curv
+        for s, p_ids in zip(f['sv_id'], f['sv2point']):
+            scores[s] = point_score[p_ids].mean()
+            feats[s] = feat[p_ids].mean(0)
+            pnums[s] = len(p_ids)
+    assert np.array_equal(board.sv_feats, feats) and np.array_equal(board.sv_pnums, pnums)
+    ulps = np.abs(board.sv_scores.view(np.int32).astype(np.int64) - scores.view(np.int32).astype(np.int64))
+    assert ulps.max() <= SCORE_ULPS
+    flags_in = np.zeros(n_sv, int)
+    flags_in[::7] = 1
+    kw = dict(trim_rate=0.8, num_clusters=6)
+    n_points = int(pnums.sum() * 100 * 0.3)          # a budget that binds inside the candidates
+    got = board.select(flags_in, n_points, **kw)
+    # the restatement clusters the same candidates (the device's scores decide the order, as in select_redal)
+    unl = np.where(flags_in == 0)[0]
+    cand = unl[np.argsort(board.sv_scores[unl])[::-1]][:int(unl.size * 0.8)]
+    r_labels, _ = redal_ref.kmeans(board.sv_feats[cand], 6, random_state=0, n_init=10)
+    want = select_redal(flags_in, board.sv_scores, board.sv_feats, board.sv_pnums, n_points, labels=r_labels, **kw)
+    assert np.array_equal(got, want)
+    assert 0 < (got == 1).sum() - (flags_in == 1).sum() < cand.size
