@@ -561,7 +561,8 @@ int lidal_supervoxel_reduce(const double* interd, const float* intere, const dou
 /* ---- ReDAL region selection (score/sv_level/ReDAL.py, dataset/ReDAL/gen_surface_variation_sk.py; csrc/redal.hip) ---- */
 /* k nearest OTHER points of every point of a raw scan xyz f32 [p,3]: knn i32 [p,k], sorted by (f64 distance, index).
  * 1 <= k <= 64; p < k + 1 is refused (status 2, lidal_last_error).  `cell`: the search grid's cell in metres (the
- * result does not depend on it).  Workspace: lidal_knn_workspace_bytes(p). */
+ * result does not depend on it).  Precondition, not checked here: every coordinate is finite (lidal_amd.score.redal
+ * checks it; a NaN query never fills its list).  Workspace: lidal_knn_workspace_bytes(p). */
 int64_t lidal_knn_workspace_bytes(int64_t p);
 int lidal_knn(const float* xyz, int64_t p, int k, double cell, int32_t* knn, void* ws, int64_t ws_bytes, void* stream);
 /* surface variation of every point: lambda_min / (lambda_1 + lambda_2 + lambda_3) of the population covariance of its

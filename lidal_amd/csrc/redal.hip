@@ -257,9 +257,48 @@ __global__ void __launch_bounds__(256) point_score_kernel(const float* __restric
   score[i] = __fadd_rn(__fmul_rn(alpha, u), __fmul_rn(gamma, curv[i]));
 }
 
-// one workgroup per supervoxel: score = point_score[p_ids].mean() (numpy's pairwise tree over the gathered values, by
-// lane 0 with an explicit stack in LDS), feats = outfeat[p_ids].mean(0) (a sequential f32 sum over the rows, one lane per
-// feature), pnum = len(p_ids)
+// numpy's f32 mean of n values get(0 .. n) of a contiguous array, by one lane: np.add.reduce does not run one pairwise
+// tree over the whole array; its iterator hands the inner loop blocks of at most 8192 values (the ufunc buffer size),
+// each summed with the pairwise tree, and the block sums are added in order to 0.  The tree of each block is walked
+// post-order with an explicit stack (st_*: 64 entries in LDS; a block of 8192 needs 7 levels).
+constexpr int64_t NP_BUFSIZE = 8192;
+template <class Get>
+__device__ float np_mean_f32(Get get, int64_t n, int64_t* st_off, int64_t* st_n, int* st_phase, float* st_val) {
+  float total = 0.f;
+  for (int64_t b0 = 0; b0 < n; b0 += NP_BUFSIZE) {
+    // one block: a leaf if <= 128 values, else split at n2 = n/2 - (n/2) % 8
+    int sp = 0, vp = 0;
+    st_off[0] = b0; st_n[0] = n - b0 < NP_BUFSIZE ? n - b0 : NP_BUFSIZE; st_phase[0] = 0; sp = 1;
+    while (sp > 0) {
+      const int top = sp - 1;
+      const int64_t o = st_off[top], m = st_n[top];
+      if (m <= 128) {
+        st_val[vp++] = np_leaf_f32(get, o, m);
+        --sp;
+        continue;
+      }
+      int64_t m2 = m / 2;
+      m2 -= m2 % 8;
+      if (st_phase[top] == 0) {
+        st_phase[top] = 1;
+        st_off[sp] = o; st_n[sp] = m2; st_phase[sp] = 0; ++sp;
+      } else if (st_phase[top] == 1) {
+        st_phase[top] = 2;
+        st_off[sp] = o + m2; st_n[sp] = m - m2; st_phase[sp] = 0; ++sp;
+      } else {
+        const float rgt = st_val[--vp], lft = st_val[--vp];
+        st_val[vp++] = __fadd_rn(lft, rgt);
+        --sp;
+      }
+    }
+    total = __fadd_rn(total, st_val[0]);
+  }
+  return __fdiv_rn(total, (float)n);       // n == 0: 0 / 0 = NaN, as numpy's mean of an empty selection
+}
+
+// one workgroup per supervoxel: score = point_score[p_ids].mean() (np_mean_f32, lane 0), feats = outfeat[p_ids].mean(0),
+// pnum = len(p_ids).  numpy reduces the rows of an [n, d >= 2] array one after the other, so the feature mean is a
+// sequential f32 sum over the rows, one lane per feature; an [n, 1] array is reduced as a contiguous one (np_mean_f32).
 constexpr int REG_BLOCK = 128;
 __global__ void __launch_bounds__(REG_BLOCK)
 region_reduce_kernel(const float* __restrict__ score, const float* __restrict__ feat, int d,
@@ -271,40 +310,17 @@ region_reduce_kernel(const float* __restrict__ score, const float* __restrict__ 
   const int s = blockIdx.x, tid = threadIdx.x;
   const int64_t beg = sv_ptr[s], end = sv_ptr[s + 1], n = end - beg;
   const float fn = (float)n;
-  for (int f = tid; f < d; f += REG_BLOCK) {
-    float acc = 0.f;
-    for (int64_t t = beg; t < end; ++t) acc = __fadd_rn(acc, feat[sv_idx[t] * d + f]);
-    sv_feats[(int64_t)s * d + f] = __fdiv_rn(acc, fn);
-  }
+  if (d > 1)
+    for (int f = tid; f < d; f += REG_BLOCK) {
+      float acc = 0.f;
+      for (int64_t t = beg; t < end; ++t) acc = __fadd_rn(acc, feat[sv_idx[t] * d + f]);
+      sv_feats[(int64_t)s * d + f] = __fdiv_rn(acc, fn);
+    }
   if (tid != 0) return;
   sv_pnums[s] = n;
-  auto get = [&](int64_t t) { return score[sv_idx[beg + t]]; };
-  // post-order walk of numpy's pairwise_sum tree: n <= 128 is a leaf, else split at n2 = n/2 - (n/2) % 8
-  int sp = 0, vp = 0;
-  st_off[0] = 0; st_n[0] = n; st_phase[0] = 0; sp = 1;
-  while (sp > 0) {
-    const int top = sp - 1;
-    const int64_t o = st_off[top], m = st_n[top];
-    if (m <= 128) {
-      st_val[vp++] = np_leaf_f32(get, o, m);
-      --sp;
-      continue;
-    }
-    int64_t m2 = m / 2;
-    m2 -= m2 % 8;
-    if (st_phase[top] == 0) {
-      st_phase[top] = 1;
-      st_off[sp] = o; st_n[sp] = m2; st_phase[sp] = 0; ++sp;
-    } else if (st_phase[top] == 1) {
-      st_phase[top] = 2;
-      st_off[sp] = o + m2; st_n[sp] = m - m2; st_phase[sp] = 0; ++sp;
-    } else {
-      const float rgt = st_val[--vp], lft = st_val[--vp];
-      st_val[vp++] = __fadd_rn(lft, rgt);
-      --sp;
-    }
-  }
-  sv_scores[s] = __fdiv_rn(st_val[0], fn);
+  if (d == 1)
+    sv_feats[s] = np_mean_f32([&](int64_t t) { return feat[sv_idx[beg + t]]; }, n, st_off, st_n, st_phase, st_val);
+  sv_scores[s] = np_mean_f32([&](int64_t t) { return score[sv_idx[beg + t]]; }, n, st_off, st_n, st_phase, st_val);
 }
 
 // ================================ k-means ================================

@@ -37,6 +37,9 @@ def _xyz(xyz):
     B.require_gpu(xyz)
     xyz = xyz.float().contiguous()
     assert xyz.ndim == 2 and xyz.shape[1] == 3, tuple(xyz.shape)
+    if not bool(torch.isfinite(xyz).all()):
+        # a NaN query never fills its list and searches until its ring covers the scan's cell box
+        raise ValueError('knn / surface_variation: the coordinates must be finite (NaN or inf found)')
     return xyz
 
 
@@ -110,6 +113,8 @@ def kmeans_single(x, n_clusters, seed, max_iter=300, tol=0.0):
     B.require_gpu(x)
     x = x.float().contiguous()
     n, d = x.shape
+    if not 1 <= n_clusters <= n:
+        raise ValueError('kmeans: n_clusters=%d must be in 1..n_samples=%d' % (n_clusters, n))
     first, u, trials = kmeans_draws(n, n_clusters, seed)
     dev = x.device
     u_dev = torch.from_numpy(u.reshape(-1).copy() if u.size else np.zeros(1)).to(dev)

@@ -1,27 +1,67 @@
-"""numpy restatement of the project's k-means definition (csrc/redal.hip) and of worker_func's
-per-region reductions: test infrastructure, the CPU side of the bit-for-bit checks."""
+"""numpy restatement of the project's k-means definition (csrc/redal.hip), of worker_func's
+per-region reductions and of the k-nearest-neighbour list and surface variation: test infrastructure, the CPU side of
+the bit-for-bit checks."""
 import numpy as np
 
 CHUNK = 256
+NP_BUFSIZE = 8192       # numpy's ufunc buffer size: an add-reduce sees blocks of at most this many values
+SHIFT_LANES = 256       # km_shift_kernel's workgroup
+
+
+def np_pairwise_f32(a):
+    """numpy's pairwise_sum of f32 values a [n]: n < 8 summed in order from 0; n <= 128 a leaf with 8 accumulators over
+    whole blocks of 8, combined ((0+1)+(2+3))+((4+5)+(6+7)), then the rest in order; else the two halves split at
+    n/2 - (n/2) % 8."""
+    f = np.float32
+    n = a.size
+    if n < 8:
+        r = f(0)
+        for v in a:
+            r = f(r + v)
+        return r
+    if n <= 128:
+        n8 = n - n % 8
+        r = a[:8].copy()
+        for i in range(8, n8, 8):
+            r = r + a[i:i + 8]
+        res = f(f(f(r[0] + r[1]) + f(r[2] + r[3])) + f(f(r[4] + r[5]) + f(r[6] + r[7])))
+        for v in a[n8:]:
+            res = f(res + v)
+        return res
+    n2 = n // 2
+    n2 -= n2 % 8
+    return f(np_pairwise_f32(a[:n2]) + np_pairwise_f32(a[n2:]))
+
+
+def np_mean_f32(values):
+    """numpy's mean of a contiguous f32 array, written out: the pairwise tree over each block of 8192 values, the block
+    sums added in order to 0, divided by f32(n).  (Not one tree over the whole array: numpy's reduce iterator hands its
+    inner loop at most one buffer of 8192 values at a time.)"""
+    a = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    total = np.float32(0)
+    for b in range(0, a.size, NP_BUFSIZE):
+        total = np.float32(total + np_pairwise_f32(a[b:b + NP_BUFSIZE]))
+    return np.float32(total / np.float32(a.size))
 
 
 def d2(x64, c):
-    """f64 squared distance of every row of x64 [N,D] to c [D]: numpy's pairwise order over the D terms, written out
-    (8 accumulators over whole blocks of 8, combined ((0+1)+(2+3))+((4+5)+(6+7)), then the rest in order)."""
+    """f64 squared distance of every row of x64 [N,D] to c [D] (or [..., D], broadcast): numpy's pairwise order over the
+    D terms, written out (8 accumulators over whole blocks of 8, combined ((0+1)+(2+3))+((4+5)+(6+7)), then the rest in
+    order)."""
     sq = (x64 - c) ** 2
-    d = sq.shape[1]
+    d = sq.shape[-1]
     if d < 8:
-        r = np.zeros(sq.shape[0])
+        r = np.zeros(sq.shape[:-1])
         for f in range(d):
-            r = r + sq[:, f]
+            r = r + sq[..., f]
         return r
     d8 = d - d % 8
-    r = sq[:, :8].copy()
+    r = sq[..., :8].copy()
     for i in range(8, d8, 8):
-        r = r + sq[:, i:i + 8]
-    res = ((r[:, 0] + r[:, 1]) + (r[:, 2] + r[:, 3])) + ((r[:, 4] + r[:, 5]) + (r[:, 6] + r[:, 7]))
+        r = r + sq[..., i:i + 8]
+    res = ((r[..., 0] + r[..., 1]) + (r[..., 2] + r[..., 3])) + ((r[..., 4] + r[..., 5]) + (r[..., 6] + r[..., 7]))
     for f in range(d8, d):
-        res = res + sq[:, f]
+        res = res + sq[..., f]
     return res
 
 
@@ -62,7 +102,9 @@ def seed(x, k, seed_):
 
 
 def assign(x64, centers):
-    dist = np.stack([d2(x64, c) for c in centers], axis=1)
+    step = max(1, (1 << 22) // max(1, x64.size))
+    dist = np.concatenate([d2(x64[:, None, :], centers[None, j:j + step]) for j in range(0, len(centers), step)],
+                          axis=1)
     labels = np.argmin(dist, axis=1)
     return labels, dist[np.arange(len(x64)), labels]
 
@@ -78,18 +120,45 @@ def relocate(labels, mind2, k):
 
 
 def update(x64, labels, centers):
+    """Sequential f64 sum of each cluster's rows in row order, divided by the count; an empty cluster keeps its
+    centre."""
     out = centers.copy()
-    for j in range(len(centers)):
-        rows = x64[labels == j]
-        if len(rows):
-            out[j] = np.cumsum(rows, axis=0)[-1] / len(rows)
+    order = np.argsort(labels, kind='stable')
+    counts = np.bincount(labels, minlength=len(centers))
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    rows = x64[order]
+    for j in np.flatnonzero(counts):
+        out[j] = np.cumsum(rows[starts[j]:starts[j] + counts[j]], axis=0)[-1] / counts[j]
     return out
 
 
-def kmeans_single(x, k, seed_, max_iter=300, tol=0.0):
-    """(labels, centers, n_iter, seeds) of one restart."""
+def shift_sum(new, old):
+    """km_shift_kernel's sum of (new - old)^2 over the k x d values (row-major): lane t of 256 sums the values t,
+    t + 256, ... in order from 0, then the fixed tree red[t] += red[t + w] for w = 128, 64, ..., 1."""
+    sq = ((new - old) ** 2).reshape(-1)
+    m = sq.size
+    pad = np.zeros(-(-m // SHIFT_LANES) * SHIFT_LANES)
+    pad[:m] = sq                                  # (+0.0 leaves a lane sum unchanged: every term is >= 0)
+    red = np.zeros(SHIFT_LANES)
+    for row in pad.reshape(-1, SHIFT_LANES):
+        red = red + row
+    w = SHIFT_LANES // 2
+    while w > 0:
+        red = np.concatenate([red[:w] + red[w:2 * w], red[w:]])
+        w //= 2
+    return float(red[0])
+
+
+def inertia_of(x64, labels, centers):
+    """The chunked (256) scan total of every row's d2 to its centre."""
+    pot, _ = scan(d2(x64, centers[labels])[None])
+    return float(pot[0])
+
+
+def lloyd(x, seeds, max_iter=300, tol=0.0):
+    """Lloyd iterations from the seed rows: (labels, centers, n_iter, inertia)."""
     x64 = x.astype(np.float64)
-    seeds = seed(x, k, seed_)
+    k = len(seeds)
     centers = x64[seeds].copy()
     old = np.full(len(x64), -1)
     strict, it = False, 0
@@ -98,7 +167,7 @@ def kmeans_single(x, k, seed_, max_iter=300, tol=0.0):
         labels, mind2 = assign(x64, centers)
         labels = relocate(labels, mind2, k)
         new = update(x64, labels, centers)
-        shift = ((new - centers) ** 2).sum()
+        shift = shift_sum(new, centers)
         centers = new
         it += 1
         if np.array_equal(labels, old):
@@ -109,18 +178,52 @@ def kmeans_single(x, k, seed_, max_iter=300, tol=0.0):
         old = labels
     if not strict:
         labels, _ = assign(x64, centers)
-    return labels, centers, it, seeds
+    return labels, centers, it, inertia_of(x64, labels, centers)
+
+
+def kmeans_single(x, k, seed_, max_iter=300, tol=0.0):
+    """(labels, centers, n_iter, seeds, inertia) of one restart; tol is absolute."""
+    seeds = seed(x, k, seed_)
+    labels, centers, it, inertia = lloyd(x, seeds, max_iter, tol)
+    return labels, centers, it, seeds, inertia
 
 
 def kmeans(x, k, random_state=0, n_init=10, max_iter=300, tol=1e-4):
+    """(labels, inertia) of the restart of least inertia, the first on ties."""
     tol_abs = float(np.var(x.astype(np.float64), axis=0).mean()) * tol
     best = None
     for s in np.random.RandomState(random_state).randint(2 ** 31 - 1, size=n_init):
-        labels, centers, it, _ = kmeans_single(x, k, int(s), max_iter, tol_abs)
-        inertia = float(((x.astype(np.float64) - centers[labels]) ** 2).sum())
+        labels, _, _, _, inertia = kmeans_single(x, k, int(s), max_iter, tol_abs)
         if best is None or inertia < best[1]:
             best = (labels, inertia)
     return best
+
+
+def knn_brute(xyz, k, block=256):
+    """The k nearest OTHER points of every point of xyz f32 [P,3] as the kernel defines them: coordinates widened to
+    f64, d2 = (dx*dx + dy*dy) + dz*dz with every product and sum rounded, ordered by (d2, index).  i32 [P,k]."""
+    x = np.asarray(xyz, dtype=np.float32).astype(np.float64)
+    p = len(x)
+    out = np.empty((p, k), np.int32)
+    for b in range(0, p, block):
+        q = x[b:b + block]
+        e = x[None, :, :] - q[:, None, :]
+        dist = (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]
+        dist[np.arange(len(q)), np.arange(b, b + len(q))] = np.inf          # the query itself
+        kth = np.partition(dist, k - 1, axis=1)[:, k - 1]
+        for r in range(len(q)):
+            cand = np.flatnonzero(dist[r] <= kth[r])                     # ascending index
+            out[b + r] = cand[np.argsort(dist[r, cand], kind='stable')[:k]]
+    return out
+
+
+def surface_variation_f64(xyz, nb):
+    """lambda_min / (l0 + l1 + l2) of the population covariance of each point's neighbours nb [P,k] (f64, LAPACK)."""
+    x = np.asarray(xyz, dtype=np.float32).astype(np.float64)[nb]
+    e = x - x.mean(axis=1, keepdims=True)
+    cov = np.einsum('pki,pkj->pij', e, e) / nb.shape[1]
+    lam = np.linalg.eigvalsh(cov)
+    return lam[:, 0] / lam.sum(axis=1)
 
 
 def same_partition(a, b):

@@ -101,3 +101,99 @@ def test_product_path_imports_no_sklearn_scipy_or_oracle():
             'print(bad); sys.exit(1 if bad else 0)')
     r = subprocess.run([sys.executable, '-c', code], cwd=ROOT, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
+
+
+def test_np_mean_f32_equals_numpy_mean():
+    """The restatement of numpy's f32 mean (pairwise trees over blocks of 8192, the block sums added in order) equals
+    numpy's own mean bit for bit, across the leaf, tree and block borders.  A numpy that changes its order fails
+    here."""
+    rs = np.random.RandomState(5)
+    pool = rs.uniform(0, 1, 600000).astype(np.float32)
+    for n in (1, 7, 8, 9, 127, 128, 129, 1254, 8191, 8192, 8193, 16384, 16385, 100000, 300001):
+        a = pool[rs.permutation(pool.size)[:n]]                 # gathered, as point_score[p_ids]
+        assert redal_ref.np_mean_f32(a) == a.mean(), n
+        assert redal_ref.np_mean_f32(a).dtype == np.float32
+    a = pool[:20000]
+    single = np.float32(redal_ref.np_pairwise_f32(a) / np.float32(a.size))
+    assert single != a.mean()                                   # one tree over the whole array is not numpy's order
+
+
+def test_np_mean_f32_is_numpys_column_mean_of_one_wide_rows():
+    """worker_func's feature mean: numpy sums the rows of an [n, d >= 2] array in sequence, but reduces an [n, 1] array
+    as a contiguous one (the order of np_mean_f32)."""
+    rs = np.random.RandomState(6)
+    a = rs.normal(size=(9000, 1)).astype(np.float32)
+    assert a.mean(0)[0] == redal_ref.np_mean_f32(a[:, 0])
+    acc = np.zeros(1, np.float32)
+    for r in a:
+        acc = acc + r
+    assert (acc / np.float32(len(a)))[0] != a.mean(0)[0]
+    b = rs.normal(size=(9000, 2)).astype(np.float32)
+    acc = np.zeros(2, np.float32)
+    for r in b:
+        acc = acc + r
+    assert np.array_equal(acc / np.float32(len(b)), b.mean(0))
+
+
+def test_shift_sum_restates_the_lane_tree():
+    """redal_ref.shift_sum against the kernel's loops written out one value at a time."""
+    rs = np.random.RandomState(7)
+    for m in (1, 5, 255, 256, 257, 1000, 150 * 96):
+        a, b = rs.normal(size=m), rs.normal(size=m)
+        red = [0.0] * 256
+        for t in range(256):
+            for i in range(t, m, 256):
+                red[t] = red[t] + (a[i] - b[i]) * (a[i] - b[i])
+        w = 128
+        while w > 0:
+            for t in range(w):
+                red[t] = red[t] + red[t + w]
+            w //= 2
+        assert redal_ref.shift_sum(a, b) == red[0], m
+        assert np.isclose(red[0], ((a - b) ** 2).sum(), rtol=1e-12)
+
+
+def test_knn_brute_orders_by_distance_then_index():
+    """knn_brute on a lattice with massive exact ties and a block of coincident points equals a full stable sort of
+    every row, and excludes the query itself."""
+    g = np.arange(-3, 3) * 0.25
+    lat = np.stack(np.meshgrid(g, g, g, indexing='ij'), -1).reshape(-1, 3)
+    xyz = np.concatenate([lat, np.zeros((20, 3))]).astype(np.float32)
+    x = xyz.astype(np.float64)
+    for k in (1, 7, 26, 64):
+        nb = redal_ref.knn_brute(xyz, k, block=50)
+        for i in range(len(x)):
+            e = x - x[i]
+            dist = (e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2]
+            dist[i] = np.inf
+            assert np.array_equal(nb[i], np.argsort(dist, kind='stable')[:k]), (k, i)
+
+
+def test_surface_variation_f64_degenerate_neighbourhoods():
+    g = np.arange(-4, 5, dtype=np.float64)
+    cube = np.stack(np.meshgrid(g, g, g, indexing='ij'), -1).reshape(-1, 3)
+    nb = redal_ref.knn_brute(cube, 32)
+    centre = int(np.flatnonzero((cube == 0).all(1))[0])
+    d2 = (cube[nb[centre]] ** 2).sum(1)
+    assert sorted(np.bincount(d2.astype(int)).tolist()) == sorted([0, 6, 12, 8, 6])     # closed shells 1, 2, 3, 4
+    assert abs(redal_ref.surface_variation_f64(cube, nb)[centre] - 1 / 3) <= 1e-12
+    line = np.zeros((40, 3), np.float32)
+    line[:, 1] = np.arange(40) * 0.3
+    assert np.allclose(redal_ref.surface_variation_f64(line, redal_ref.knn_brute(line, 10)), 0.0, atol=1e-15)
+
+
+def test_kmeans_restatement_inertia_and_tol():
+    """kmeans_single's inertia is the chunked scan of every row's d2 to its returned centre (close to the plain sum);
+    a tolerance above 0 stops no later than tol = 0."""
+    x = RI.overlapping()[:1000]
+    s = int(np.random.RandomState(0).randint(2 ** 31 - 1, size=10)[0])
+    labels, centers, it0, seeds, inertia = redal_ref.kmeans_single(x, 20, s)
+    x64 = x.astype(np.float64)
+    assert np.isclose(inertia, ((x64 - centers[labels]) ** 2).sum(), rtol=1e-12)
+    assert inertia == redal_ref.inertia_of(x64, labels, centers)
+    tol = float(np.var(x64, axis=0).mean()) * 1e-4
+    _, _, it1, seeds1, _ = redal_ref.kmeans_single(x, 20, s, tol=tol)
+    assert np.array_equal(seeds, seeds1) and 1 <= it1 <= it0
+    labels0, centers0, it, inertia0 = redal_ref.lloyd(x, seeds, max_iter=0)
+    assert it == 0 and np.array_equal(centers0, x64[seeds])
+    assert np.array_equal(labels0, redal_ref.assign(x64, centers0)[0])

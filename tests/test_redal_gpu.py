@@ -96,12 +96,13 @@ def test_kmeans_seeds_and_one_step_equal_restatement():
     s = _seed0()
     xd = torch.from_numpy(x).to(DEV)
     for it in (0, 1):
-        labels, centers, _, n_iter, seeds = kmeans_single(xd, 150, s, max_iter=it, tol=0.0)
-        r_labels, r_centers, r_it, r_seeds = redal_ref.kmeans_single(x, 150, s, max_iter=it)
+        labels, centers, inertia, n_iter, seeds = kmeans_single(xd, 150, s, max_iter=it, tol=0.0)
+        r_labels, r_centers, r_it, r_seeds, r_inertia = redal_ref.kmeans_single(x, 150, s, max_iter=it)
         assert np.array_equal(seeds.cpu().numpy(), r_seeds)
         assert np.array_equal(labels.cpu().numpy(), r_labels)
         assert np.array_equal(centers.cpu().numpy(), r_centers)
         assert n_iter == r_it == it
+        assert inertia == r_inertia
 
 
 def test_kmeans_partitions_blobs_like_sklearn(golden_dir):
@@ -141,12 +142,12 @@ def test_kmeans_relocates_empty_cluster():
     xd = torch.from_numpy(x).to(DEV)
     for it in (1, 2, 5):
         labels, centers, inertia, n_iter, seeds = kmeans_single(xd, 4, 7, max_iter=it, tol=0.0)
-        r_labels, r_centers, r_it, r_seeds = redal_ref.kmeans_single(x, 4, 7, max_iter=it)
+        r_labels, r_centers, r_it, r_seeds, r_inertia = redal_ref.kmeans_single(x, 4, 7, max_iter=it)
         assert np.array_equal(seeds.cpu().numpy(), r_seeds)
         assert len(np.unique(x[r_seeds], axis=0)) < 4   # two seeds on the same point: the case under test
         assert np.array_equal(labels.cpu().numpy(), r_labels)
         assert np.array_equal(centers.cpu().numpy(), r_centers)
-        assert n_iter == r_it and np.isfinite(inertia)
+        assert n_iter == r_it and np.isfinite(inertia) and inertia == r_inertia
 
 
 def test_redal_sequence_board_and_selection():
