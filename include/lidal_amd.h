@@ -587,6 +587,33 @@ int lidal_kmeans(const float* x, int64_t n, int d, int k, int64_t first, const d
                  double tol, int32_t* seeds, int32_t* labels, double* centers, double* inertia_host,
                  int32_t* n_iter_host, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- frame-level selection (score/frame_level/ of the reference; csrc/frame_level.hip) ---------------------- */
+/* softmax_entropy.py, margin_sampling.py, least_confidence_sampling.py worker_func for one frame, prob f32 [p,c]
+ * (2 <= c <= 32): out f32 [3] = (np.mean(entropy(prob, axis=1)), np.mean(top1 - top2), np.mean(top1)), numpy's
+ * orders (pairwise row sums, blocked f32 means), entr in f64 rounded to f32.  Precondition, not checked here: prob is
+ * finite (lidal_amd.score.frame_level checks it).  Workspace: lidal_frame_uncertainty_workspace_bytes(p). */
+int64_t lidal_frame_uncertainty_workspace_bytes(int64_t p);
+int lidal_frame_uncertainty(const float* prob, int64_t p, int c, float* out, void* ws, int64_t ws_bytes, void* stream);
+/* segment_entropy.py worker_func: pred i64 [p], the supervoxel CSR (sv_ptr i64 [s+1], sv_idx i64 with values in
+ * [0, p)), 1 <= class_num <= 256 -> *out f64 (device): sum over supervoxels, in order, of sv * n / p, sv the f64
+ * log2 entropy of the predicted-class histogram (an empty supervoxel gives NaN).  Workspace:
+ * lidal_segment_entropy_workspace_bytes(s). */
+int64_t lidal_segment_entropy_workspace_bytes(int s);
+int lidal_segment_entropy(const int64_t* pred, int64_t p, const int64_t* sv_ptr, const int64_t* sv_idx, int s,
+                          int class_num, double* out, void* ws, int64_t ws_bytes, void* stream);
+/* core_set.py:66: outfeat.mean(0) of feat f32 [p,d] -> out f32 [d]: per column the sequential f32 sum of the rows
+ * (d == 1: numpy's blocked pairwise mean of the contiguous column).  Workspace: lidal_frame_feature_workspace_bytes(p). */
+int64_t lidal_frame_feature_workspace_bytes(int64_t p);
+int lidal_frame_feature(const float* feat, int64_t p, int d, float* out, void* ws, int64_t ws_bytes, void* stream);
+/* core_set.py:74-92, the greedy k-center over feats f32 [n,d] (d <= 128) from the labeled rows labeled i64
+ * [n_labeled >= 1] (device): picks i64 [num_add] in pick order and the final min_dist f32 [n].  dist = f32 sqrt of
+ * f32(the pairwise-order f64 sum of squared differences); argmax takes the lowest row on ties.  status_dev i32 [2]:
+ * [0] = t > 0 if pick t (1-based) was already selected (the reference asserts), [1] = labeled ids outside [0, n).
+ * num_add <= n - n_labeled.  Workspace: lidal_coreset_workspace_bytes(n, num_add). */
+int64_t lidal_coreset_workspace_bytes(int64_t n, int num_add);
+int lidal_coreset(const float* feats, int64_t n, int d, const int64_t* labeled, int64_t n_labeled, int num_add,
+                  int64_t* picks, float* min_dist, int32_t* status_dev, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- row-wise helpers of a planned step (what torch glue did between the operators) ------------- */
 /* dst[r][0 : row_bytes) = src[r][0 : row_bytes), dst[r][row_bytes : row_bytes + zero_bytes) = 0 for r < rows; rows
  * `src_pitch` / `dst_pitch` bytes apart.  One call per summand is torchsparse.cat (operators.py; network/spvcnn.py:

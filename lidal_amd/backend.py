@@ -146,6 +146,14 @@ SIGNATURES = {
     'lidal_kmeans_workspace_bytes': (_i64, [_i64, _i32, _i32, _i32]),
     'lidal_kmeans': (_i32, [_vp, _i64, _i32, _i32, _i64, _vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                             _vp]),
+    'lidal_frame_uncertainty_workspace_bytes': (_i64, [_i64]),
+    'lidal_frame_uncertainty': (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _vp]),
+    'lidal_segment_entropy_workspace_bytes': (_i64, [_i32]),
+    'lidal_segment_entropy': (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _vp]),
+    'lidal_frame_feature_workspace_bytes': (_i64, [_i64]),
+    'lidal_frame_feature': (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _vp]),
+    'lidal_coreset_workspace_bytes': (_i64, [_i64, _i32]),
+    'lidal_coreset': (_i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     'lidal_copy2d': (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp]),
     'lidal_add2d': (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp]),
     'lidal_transpose_f32': (_i32, [_vp, _i64, _vp, _i32, _i32, _vp]),

@@ -12,9 +12,11 @@
 
 #include "common.h"
 #include "grid.h"
+#include "npsum.h"
 
 using namespace lidal;
 using namespace lidal::grid;
+using namespace lidal::npsum;
 
 extern "C" int64_t lidal_nn_grid_bytes(int64_t p);
 extern "C" int64_t lidal_nn_grid_workspace_bytes(int64_t p);
@@ -212,31 +214,6 @@ knn_kernel(KnnGrid g, const double* __restrict__ pts, int k, const int* __restri
 // ================================ region scores (ReDAL.py worker_func) ================================
 constexpr int MAXC = 32;
 
-// numpy's pairwise float32 add-reduce of n <= 128 values a[0..n) (as score.hip's np_sum_f32), element t read by get(t)
-template <class Get>
-__device__ __forceinline__ float np_leaf_f32(Get get, int64_t off, int64_t n) {
-  if (n < 8) {
-    float r = 0.f;
-    for (int64_t i = 0; i < n; ++i) r = __fadd_rn(r, get(off + i));
-    return r;
-  }
-  float r[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = get(off + j);
-  int64_t i = 8;
-  for (; i < n - (n % 8); i += 8)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = __fadd_rn(r[j], get(off + i + j));
-  float res = __fadd_rn(__fadd_rn(__fadd_rn(r[0], r[1]), __fadd_rn(r[2], r[3])),
-                        __fadd_rn(__fadd_rn(r[4], r[5]), __fadd_rn(r[6], r[7])));
-  for (; i < n; ++i) res = __fadd_rn(res, get(off + i));
-  return res;
-}
-
-__device__ __forceinline__ float np_sum_f32(const float* a, int n) {
-  return np_leaf_f32([&](int64_t t) { return a[t]; }, 0, n);
-}
-
 // per point: uncertain = mean_c(-p * log2(p + 1e-12)) (f32 terms, pairwise class sum, divided by C), then
 // point_score = alpha * uncertain + gamma * curvature (ReDAL.py:59-63).  log2 is taken in f64 and rounded (numpy's f32
 // log2 may dispatch to a SIMD routine that differs in the last bit: the one step not restated).
@@ -255,45 +232,6 @@ __global__ void __launch_bounds__(256) point_score_kernel(const float* __restric
     }
   const float u = __fdiv_rn(np_sum_f32(term, c), (float)c);
   score[i] = __fadd_rn(__fmul_rn(alpha, u), __fmul_rn(gamma, curv[i]));
-}
-
-// numpy's f32 mean of n values get(0 .. n) of a contiguous array, by one lane: np.add.reduce does not run one pairwise
-// tree over the whole array; its iterator hands the inner loop blocks of at most 8192 values (the ufunc buffer size),
-// each summed with the pairwise tree, and the block sums are added in order to 0.  The tree of each block is walked
-// post-order with an explicit stack (st_*: 64 entries in LDS; a block of 8192 needs 7 levels).
-constexpr int64_t NP_BUFSIZE = 8192;
-template <class Get>
-__device__ float np_mean_f32(Get get, int64_t n, int64_t* st_off, int64_t* st_n, int* st_phase, float* st_val) {
-  float total = 0.f;
-  for (int64_t b0 = 0; b0 < n; b0 += NP_BUFSIZE) {
-    // one block: a leaf if <= 128 values, else split at n2 = n/2 - (n/2) % 8
-    int sp = 0, vp = 0;
-    st_off[0] = b0; st_n[0] = n - b0 < NP_BUFSIZE ? n - b0 : NP_BUFSIZE; st_phase[0] = 0; sp = 1;
-    while (sp > 0) {
-      const int top = sp - 1;
-      const int64_t o = st_off[top], m = st_n[top];
-      if (m <= 128) {
-        st_val[vp++] = np_leaf_f32(get, o, m);
-        --sp;
-        continue;
-      }
-      int64_t m2 = m / 2;
-      m2 -= m2 % 8;
-      if (st_phase[top] == 0) {
-        st_phase[top] = 1;
-        st_off[sp] = o; st_n[sp] = m2; st_phase[sp] = 0; ++sp;
-      } else if (st_phase[top] == 1) {
-        st_phase[top] = 2;
-        st_off[sp] = o + m2; st_n[sp] = m - m2; st_phase[sp] = 0; ++sp;
-      } else {
-        const float rgt = st_val[--vp], lft = st_val[--vp];
-        st_val[vp++] = __fadd_rn(lft, rgt);
-        --sp;
-      }
-    }
-    total = __fadd_rn(total, st_val[0]);
-  }
-  return __fdiv_rn(total, (float)n);       // n == 0: 0 / 0 = NaN, as numpy's mean of an empty selection
 }
 
 // one workgroup per supervoxel: score = point_score[p_ids].mean() (np_mean_f32, lane 0), feats = outfeat[p_ids].mean(0),
@@ -325,40 +263,8 @@ region_reduce_kernel(const float* __restrict__ score, const float* __restrict__ 
 
 // ================================ k-means ================================
 constexpr int KM_CHUNK = 256;     // the scan of D^2: sequential inside chunks of 256, then sequential over the chunks
-constexpr int KM_DMAX = 128;
+constexpr int KM_DMAX = NP_DMAX;
 
-// numpy's pairwise f64 sum of the squared differences of one row (f32, widened) and one centre (f64), d <= 128:
-// r[j] = sq[j]; r[j] += sq[i + j] for whole blocks of 8; ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)); the rest in order.
-template <class C>
-__device__ __forceinline__ double km_d2(const float (&x)[KM_DMAX], C cget, int d) {
-  const int d8 = d - d % 8;
-  if (d < 8) {
-    double r = 0.0;
-#pragma unroll
-    for (int f = 0; f < 8; ++f)
-      if (f < d) { const double e = (double)x[f] - cget(f); r = __dadd_rn(r, __dmul_rn(e, e)); }
-    return r;
-  }
-  double r[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { const double e = (double)x[j] - cget(j); r[j] = __dmul_rn(e, e); }
-#pragma unroll
-  for (int i = 8; i < KM_DMAX; i += 8)
-    if (i < d8)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { const double e = (double)x[i + j] - cget(i + j); r[j] = __dadd_rn(r[j], __dmul_rn(e, e)); }
-  double res = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
-                         __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-#pragma unroll
-  for (int f = 0; f < KM_DMAX; ++f)
-    if (f >= d8 && f < d) { const double e = (double)x[f] - cget(f); res = __dadd_rn(res, __dmul_rn(e, e)); }
-  return res;
-}
-
-__device__ __forceinline__ void km_load_row(const float* __restrict__ x, int64_t i, int d, float (&r)[KM_DMAX]) {
-#pragma unroll
-  for (int f = 0; f < KM_DMAX; ++f) r[f] = f < d ? x[i * d + f] : 0.f;
-}
 
 __global__ void km_first_seed_kernel(int* __restrict__ seeds, int first) {
   if (threadIdx.x == 0) seeds[0] = first;
@@ -370,8 +276,8 @@ __global__ void __launch_bounds__(256) km_first_kernel(const float* __restrict__
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float r[KM_DMAX];
-  km_load_row(x, i, d, r);
-  closest[i] = km_d2(r, [&](int f) { return (double)x[first * d + f]; }, d);
+  load_row_f32(x, i, d, r);
+  closest[i] = np_d2_f64(r, [&](int f) { return (double)x[first * d + f]; }, d);
 }
 
 // tot[r][c] = sequential sum of src[r][c * 256 .. ) (the last value of the chunk's inclusive scan)
@@ -439,11 +345,11 @@ __global__ void __launch_bounds__(256) km_trial_kernel(const float* __restrict__
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float r[KM_DMAX];
-  km_load_row(x, i, d, r);
+  load_row_f32(x, i, d, r);
   const double ci = closest[i];
   for (int t = 0; t < trials; ++t) {
     const int64_t cj = cand[t];
-    const double v = km_d2(r, [&](int f) { return (double)x[cj * d + f]; }, d);
+    const double v = np_d2_f64(r, [&](int f) { return (double)x[cj * d + f]; }, d);
     D[(int64_t)t * n + i] = v < ci ? v : ci;
   }
 }
@@ -483,12 +389,12 @@ __global__ void __launch_bounds__(256) km_assign_kernel(const float* __restrict_
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float r[KM_DMAX];
-  km_load_row(x, i, d, r);
+  load_row_f32(x, i, d, r);
   double best = INFINITY;
   int arg = 0;
   for (int j = 0; j < k; ++j) {
     const double* c = centers + (int64_t)j * d;
-    const double v = km_d2(r, [&](int f) { return c[f]; }, d);
+    const double v = np_d2_f64(r, [&](int f) { return c[f]; }, d);
     if (v < best) { best = v; arg = j; }
   }
   labels[i] = arg;

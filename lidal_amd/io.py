@@ -10,6 +10,8 @@ vice versa.
   sv_flag/.../<frame>.npy      i64 [S] in {0,1,2}   LiDAL.py:328-330
   super_voxel/KMeans/sv_pnums.npy, sv_centers.npy   i64 [sum S]; f32 [sum S, 3] with the
                                +1000 * sequence-index offset      LiDAL.py:173-177,220-222
+  frame_flag/0r/<seq>.npy, frame_flag/<model>/<METRIC>/<r>r/<seq>.npy, frame_flag/RAND/<r>r/<seq>.npy
+                               bool [frames of the sequence]   score/frame_level/*.py (RAND.py writes float)
   boundary/<seq>/<frame>.npy   f32 [P]       the surface variation of a raw scan
                                dataset/ReDAL/gen_surface_variation_sk.py -> ReDAL.py:57
   <dir>/current.pt             {'model_state_dict', 'iteration', 'ep_id'}   train.py:151-155
@@ -21,7 +23,8 @@ import numpy as np
 import torch
 
 __all__ = ['save_prob_pred', 'load_prob', 'load_supervoxels', 'save_supervoxels', 'load_sv_flag',
-           'save_sv_flag', 'load_sv_stats', 'save_sv_stats', 'load_curvature', 'save_curvature', 'save_checkpoint', 'load_checkpoint']
+           'save_sv_flag', 'load_sv_stats', 'save_sv_stats', 'load_curvature', 'save_curvature', 'frame_flag_path', 'load_frame_flag',
+           'save_frame_flag', 'save_checkpoint', 'load_checkpoint']
 
 
 def _mkdir_for(path):
@@ -96,6 +99,29 @@ def save_curvature(path, curvature):
     curvature = curvature.detach().cpu().numpy() if torch.is_tensor(curvature) else np.asarray(curvature)
     _mkdir_for(path)
     np.save(path, curvature.astype(np.float32, copy=False))
+
+
+def frame_flag_path(root, dataset_name, seq, r_id, metric=None, model_name=None):
+    """The frame flags of sequence `seq` after round r_id, under root (the directory holding Processing_files):
+    frame_flag/0r for r_id == 0, frame_flag/RAND/<r>r for RAND, else frame_flag/<model>/<metric>/<r>r
+    (score/frame_level/*.py)."""
+    base = os.path.join(root, 'Processing_files', dataset_name, 'frame_flag')
+    if r_id == 0:
+        return os.path.join(base, '0r', '%s.npy' % seq)
+    if metric == 'RAND':
+        return os.path.join(base, 'RAND', '%dr' % r_id, '%s.npy' % seq)
+    return os.path.join(base, model_name, metric, '%dr' % r_id, '%s.npy' % seq)
+
+
+def load_frame_flag(path):
+    """-> bool [frames]; RAND.py's float files read as its `== False` reads them."""
+    return np.load(path) != 0
+
+
+def save_frame_flag(path, flags):
+    flags = flags.detach().cpu().numpy() if torch.is_tensor(flags) else np.asarray(flags)
+    _mkdir_for(path)
+    np.save(path, flags.astype(bool))
 
 
 def save_checkpoint(directory, model, iteration, ep_id):

@@ -1,7 +1,10 @@
 """GPU counterparts of the reference's scoring stage: score/prob_inference.py (per-frame
 view-mean probabilities) and score/sv_level/LiDAL.py (inter-frame divergence / entropy per
 supervoxel + greedy selection), with frames sharded over the GPUs of a node; and the ReDAL baseline
-(score/sv_level/ReDAL.py: surface variation, region scores, k-means, diversity-aware selection) on one GPU."""
+(score/sv_level/ReDAL.py: surface variation, region scores, k-means, diversity-aware selection) on one GPU; and the
+frame-level baselines (score/frame_level/: entropy, margin, confidence, segment entropy, core-set, random)."""
+from .frame_level import (FrameBoard, coreset, frame_feature, frame_sequence, frame_uncertainty, random_frames,
+                          segment_entropy, select_frames)
 from .interframe import FrameBank, neighbour_ids, score_frame
 from .pipeline import ScoreBoard, collect_sequence, score_sequence
 from .prob_inference import infer_frame
@@ -12,4 +15,6 @@ from .sharding import HaloExchange, frame_range, gather_frames, needed_frames
 
 __all__ = ['infer_frame', 'FrameBank', 'neighbour_ids', 'score_frame', 'score_sequence', 'collect_sequence', 'ScoreBoard', 'select',
            'frame_range', 'gather_frames', 'needed_frames', 'HaloExchange',
-           'surface_variation', 'knn', 'region_scores', 'kmeans', 'select_redal', 'RegionBoard', 'redal_sequence']
+           'surface_variation', 'knn', 'region_scores', 'kmeans', 'select_redal', 'RegionBoard', 'redal_sequence',
+           'frame_uncertainty', 'segment_entropy', 'frame_feature', 'coreset', 'select_frames', 'random_frames',
+           'frame_sequence', 'FrameBoard']
