@@ -478,9 +478,8 @@ def side_stream(device, which=1):
     if which != 1:
         key = key + (which,)
     if key not in _side_streams:
-        # (LIDAL_X_SIDE_PRIORITY=-1: the weight gradients' stream as a high-priority queue -- an experiment, profiles/README.md round 6)
-        pr = int(os.environ.get('LIDAL_X_SIDE_PRIORITY', '0')) if which == 1 else 0
-        _side_streams[key] = torch.cuda.Stream(device=device, priority=pr)
+        # (the weight gradients' stream as a high-priority queue: measured in round 6, profiles/README.md, not kept)
+        _side_streams[key] = torch.cuda.Stream(device=device)
     return _side_streams[key]
 
 
@@ -588,8 +587,9 @@ SPLIT_F32 = os.environ.get('LIDAL_F32_SPLIT', '1') != '0'
 # Round 6: the f32 TRAINING step (the reference trains in fp32, train.py:127-140) runs the forward products and the data
 # gradients of its sparse convolutions in the split form too, wherever BOTH channel counts are whole 32-channel slices
 # (one rule per layer: its forward reduces over ci, its data gradient over co) -- everything but the 4-channel stem
-# convolution; the weight gradients and the dense layers (1x1x1 convolutions, nn.Linear) keep the exact f32 MFMA.  As
-# close to the f64 oracle as the exact kernels (tests/test_benchsize_gpu.py, same calibrated bars).
+# convolution.  The forward products and data gradients of the dense layers (1x1x1 convolutions, nn.Linear) keep the exact
+# f32 MFMA; every weight gradient, dense layers included, takes the split form wherever both channel counts are multiples
+# of 8 (wgrad_code below).  As close to the f64 oracle as the exact kernels (tests/test_benchsize_gpu.py, same calibrated bars).
 # LIDAL_F32_SPLIT_TRAIN=0: the exact f32 MFMA everywhere in training (the association the round-1..5 numbers were taken with).
 SPLIT_F32_TRAIN = os.environ.get('LIDAL_F32_SPLIT_TRAIN', '1') != '0'
 
@@ -600,8 +600,7 @@ def conv_code(dt, n_red, inference, n_col=None):
     if dt == torch.float32 and SPLIT_F32 and n_red > 0 and n_red % 32 == 0:
         if inference:
             return F32_SPLIT
-        if (SPLIT_F32_TRAIN and n_col is not None and n_col > 0 and n_col % 32 == 0
-                and os.environ.get('LIDAL_X_SPLIT_APPLY') != '0'):
+        if SPLIT_F32_TRAIN and n_col is not None and n_col > 0 and n_col % 32 == 0:
             return F32_SPLIT
     return dtype_code(dt)
 

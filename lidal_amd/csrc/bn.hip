@@ -14,26 +14,11 @@ using namespace lidal;
 namespace {
 
 constexpr int NT = 256;
-#ifndef LIDAL_BN_EW_THREADS
-#define LIDAL_BN_EW_THREADS 256
-#endif
-constexpr int EW_THREADS = LIDAL_BN_EW_THREADS;   // threads of the element-wise kernels that take it as a parameter
+constexpr int EW_THREADS = 256;   // threads of the element-wise kernels that take it as a parameter
 constexpr int UNR = 4;      // row loads in flight per thread (per operand)
-// per kernel family (scripts/build_variant.py -DLIDAL_BN_UNR_x=8: the sweep of round 5, profiles/README.md): statistics
-// pass, normalising pass, backward sums, dx
-#ifndef LIDAL_BN_UNR_S
-#define LIDAL_BN_UNR_S UNR
-#endif
-#ifndef LIDAL_BN_UNR_A
-#define LIDAL_BN_UNR_A UNR
-#endif
-#ifndef LIDAL_BN_UNR_P
-#define LIDAL_BN_UNR_P UNR
-#endif
-#ifndef LIDAL_BN_UNR_D
-#define LIDAL_BN_UNR_D UNR
-#endif
-constexpr int UNR_S = LIDAL_BN_UNR_S, UNR_A = LIDAL_BN_UNR_A, UNR_P = LIDAL_BN_UNR_P, UNR_D = LIDAL_BN_UNR_D;
+// per kernel family: statistics pass, normalising pass, backward sums, dx (8 in any of them measured in round 5,
+// profiles/README.md "BatchNorm backward": families 3.77 -> 3.77-3.82 ms, not kept)
+constexpr int UNR_S = UNR, UNR_A = UNR, UNR_P = UNR, UNR_D = UNR;
 constexpr int MIN_ROWS_PER_WG = 32;    // rows per workgroup (one statistics partial each), at least
 
 template <typename T> struct IO;
@@ -342,18 +327,6 @@ __global__ void __launch_bounds__(NT) bn_bwd_partial_kernel(const T* __restrict_
       }
     };
     int64_t r = r_beg + rl;
-#ifdef LIDAL_BN_NO_PIPELINE
-    for (; r + (UNR_P - 1) * rpi < r_end; r += UNR_P * rpi) {
-      typename IO<T>::vec vx[UNR_P], vd[UNR_P];
-#pragma unroll
-      for (int u = 0; u < UNR_P; ++u) {
-        vx[u] = *reinterpret_cast<const typename IO<T>::vec*>(x + (r + u * rpi) * c + cg * VEC);
-        vd[u] = *reinterpret_cast<const typename IO<T>::vec*>(dy + (r + u * rpi) * ldy + cg * VEC);
-      }
-#pragma unroll
-      for (int u = 0; u < UNR_P; ++u) one(vx[u], vd[u]);
-    }
-#else
     // two batches in flight: the loads of batch i + 1 are requested before batch i is summed -- with ONE wave per SIMD
     // (256 workgroups of 4 waves) nothing else hides the arithmetic of a batch (~90 VALU instructions per 16-byte pair,
     // f64 sums) behind the memory round trip.  Same rows, same order per thread: the sums are those of the plain loop.
@@ -380,7 +353,6 @@ __global__ void __launch_bounds__(NT) bn_bwd_partial_kernel(const T* __restrict_
 #pragma unroll
       for (int u = 0; u < UNR_P; ++u) one(vx[u], vd[u]);
     }
-#endif
     for (; r < r_end; r += rpi)
       one(*reinterpret_cast<const typename IO<T>::vec*>(x + r * c + cg * VEC),
           *reinterpret_cast<const typename IO<T>::vec*>(dy + r * ldy + cg * VEC));
@@ -768,26 +740,10 @@ static inline int rows_per_wg(int64_t n) { return slab_rows(n); }
 // everywhere.  The reducing kernels are best at 256 on every level (sweep: profiles/README.md).
 constexpr int64_t EW_WIDE_BYTES = 12ll << 20;
 static inline int rows_per_wg_ew(int64_t n, int64_t row_bytes) {
-#ifndef LIDAL_BN_EW_WGS
-#define LIDAL_BN_EW_WGS (2 * BN_WGS)
-#endif
-  const int wgs = n * row_bytes >= EW_WIDE_BYTES ? LIDAL_BN_EW_WGS : BN_WGS;
+  const int wgs = n * row_bytes >= EW_WIDE_BYTES ? 2 * BN_WGS : BN_WGS;
   int64_t rpw = (n + wgs - 1) / wgs;
   if (rpw < MIN_ROWS_PER_WG) rpw = MIN_ROWS_PER_WG;
   return (int)rpw;
-}
-// the forward (apply) kernels alone: A/B knob for their grid (LIDAL_BN_APPLY_WGS, 0 = as the other element-wise kernels)
-#ifndef LIDAL_BN_APPLY_WGS
-#define LIDAL_BN_APPLY_WGS 0
-#endif
-static inline int rows_per_wg_apply(int64_t n, int64_t row_bytes) {
-  if (LIDAL_BN_APPLY_WGS == 0 || n * row_bytes < EW_WIDE_BYTES / 4) return rows_per_wg_ew(n, row_bytes);
-  int64_t rpw = (n + LIDAL_BN_APPLY_WGS - 1) / LIDAL_BN_APPLY_WGS;
-  if (rpw < MIN_ROWS_PER_WG) rpw = MIN_ROWS_PER_WG;
-  return (int)rpw;
-}
-static inline int nslabs_apply(int64_t n, int64_t row_bytes) {
-  return (int)cdiv(n > 0 ? n : 1, rows_per_wg_apply(n, row_bytes));
 }
 static inline int nslabs_ew(int64_t n, int64_t row_bytes) {
   return (int)cdiv(n > 0 ? n : 1, rows_per_wg_ew(n, row_bytes));
@@ -805,9 +761,9 @@ int bn_train_fwd(const void* x, int64_t n, int c, const float* gamma, const floa
   bn_stats_final_kernel<double><<<(unsigned)cdiv(c, 8), NT, 0, s>>>(part, np, c, eps, momentum, mean,
                                                              invstd, rm, rv, nbt);
   LIDAL_CHECK_LAUNCH("bn_stats_final");
-  bn_apply_kernel<T, false><<<nslabs_apply(n, (int64_t)c * sizeof(T)), NT, 0, s>>>((const T*)x, n, c, mean, invstd, gamma,
+  bn_apply_kernel<T, false><<<nslabs_ew(n, (int64_t)c * sizeof(T)), NT, 0, s>>>((const T*)x, n, c, mean, invstd, gamma,
                                                         beta, eps, relu, (const T*)res, (T*)y,
-                                                        rows_per_wg_apply(n, (int64_t)c * sizeof(T)));
+                                                        rows_per_wg_ew(n, (int64_t)c * sizeof(T)));
   LIDAL_CHECK_LAUNCH("bn_apply");
   return 0;
 }
@@ -1469,9 +1425,9 @@ extern "C" int lidal_bn_train_fwd_tiles(const void* x, int dtype, int64_t n, int
   if (bn_fused() && c <= SLOT_CH && next_slots(&slots, s)) {
     const int flags = (relu & 1) | (residual != nullptr ? 2 : 0) | ((residual != nullptr && (relu & 2)) ? 4 : 0);
 #define LIDAL_APPLY_TILES(T, FV)                                                                                          \
-    bn_apply_tiles_kernel<T, EW_THREADS, FV><<<nslabs_apply(n, (int64_t)c * sizeof(T)), EW_THREADS, 0, s>>>(               \
+    bn_apply_tiles_kernel<T, EW_THREADS, FV><<<nslabs_ew(n, (int64_t)c * sizeof(T)), EW_THREADS, 0, s>>>(                 \
         (const T*)x, n, c, tile_stats, (int)n_tiles, eps, momentum, save_mean, save_invstd, running_mean, running_var,    \
-        (long long*)num_batches_tracked, gamma, beta, (const T*)residual, (T*)y, rows_per_wg_apply(n, (int64_t)c * sizeof(T)), \
+        (long long*)num_batches_tracked, gamma, beta, (const T*)residual, (T*)y, rows_per_wg_ew(n, (int64_t)c * sizeof(T)), \
         slots)
 #define LIDAL_APPLY_TILES_F(T)                                                        \
     switch (flags) {                                                                  \
@@ -1490,15 +1446,15 @@ extern "C" int lidal_bn_train_fwd_tiles(const void* x, int dtype, int64_t n, int
                                                    (long long*)num_batches_tracked);
   LIDAL_CHECK_LAUNCH("bn_stats_final(tiles)");
   if (dtype == LIDAL_F32)
-    bn_apply_kernel<float, false><<<nslabs_apply(n, (int64_t)c * 4), NT, 0, s>>>((const float*)x, n, c, save_mean, save_invstd,
+    bn_apply_kernel<float, false><<<nslabs_ew(n, (int64_t)c * 4), NT, 0, s>>>((const float*)x, n, c, save_mean, save_invstd,
                                                               gamma, beta, eps, relu,
                                                               (const float*)residual, (float*)y,
-                                                              rows_per_wg_apply(n, (int64_t)c * 4));
+                                                              rows_per_wg_ew(n, (int64_t)c * 4));
   else
-    bn_apply_kernel<__bf16, false><<<nslabs_apply(n, (int64_t)c * 2), NT, 0, s>>>((const __bf16*)x, n, c, save_mean,
+    bn_apply_kernel<__bf16, false><<<nslabs_ew(n, (int64_t)c * 2), NT, 0, s>>>((const __bf16*)x, n, c, save_mean,
                                                                save_invstd, gamma, beta, eps, relu,
                                                                (const __bf16*)residual, (__bf16*)y,
-                                                               rows_per_wg_apply(n, (int64_t)c * 2));
+                                                               rows_per_wg_ew(n, (int64_t)c * 2));
   LIDAL_CHECK_LAUNCH("bn_apply");
   return 0;
 }
@@ -1511,13 +1467,13 @@ extern "C" int lidal_bn_eval_fwd(const void* x, int dtype, int64_t n, int c, con
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   if (dtype == LIDAL_F32)
-    bn_apply_kernel<float, true><<<nslabs_apply(n, (int64_t)c * 4), NT, 0, s>>>(
+    bn_apply_kernel<float, true><<<nslabs_ew(n, (int64_t)c * 4), NT, 0, s>>>(
         (const float*)x, n, c, running_mean, running_var, gamma, beta, eps, relu, nullptr, (float*)y,
-        rows_per_wg_apply(n, (int64_t)c * 4));
+        rows_per_wg_ew(n, (int64_t)c * 4));
   else
-    bn_apply_kernel<__bf16, true><<<nslabs_apply(n, (int64_t)c * 2), NT, 0, s>>>(
+    bn_apply_kernel<__bf16, true><<<nslabs_ew(n, (int64_t)c * 2), NT, 0, s>>>(
         (const __bf16*)x, n, c, running_mean, running_var, gamma, beta, eps, relu, nullptr, (__bf16*)y,
-        rows_per_wg_apply(n, (int64_t)c * 2));
+        rows_per_wg_ew(n, (int64_t)c * 2));
   LIDAL_CHECK_LAUNCH("lidal_bn_eval_fwd");
   return 0;
 }

@@ -628,10 +628,10 @@ wgrad_split_kernel(const __bf16* __restrict__ a, const __bf16* __restrict__ b, u
 // The kernel is then the loop above without pieces: one uninterrupted pipeline per workgroup, two slabs at the end.
 // stages in flight per workgroup: one, as in the offset-major kernel (measured with two resident workgroups per CU and as
 // many stages as 78 KB of LDS hold -- depth 2 for 96 -> 96, 4 for 32 -> 32 -- on 397 k / 226 k rows: 96 -> 96 88 -> 98 us,
-// 64 -> 64 52 -> 53, 32 -> 32 52 -> 51.5; LIDAL_X_STREAM_DEPTH keeps the deeper ring selectable for experiments)
+// 64 -> 64 52 -> 53, 32 -> 32 52 -> 51.5: measured in round 6, profiles/r06_wgrad_streams.txt, not kept)
 constexpr int stream_depth(int /*stage_bytes*/) { return 1; }
 
-template <int MI, int NI, int DD>
+template <int MI, int NI>
 __global__ void __launch_bounds__(WT, 2)
 wgrad_stream_kernel(const __bf16* __restrict__ a, const __bf16* __restrict__ b, unsigned n_a, unsigned n_b,
                     const int2* __restrict__ spairs, const int* __restrict__ soff, const int* __restrict__ wk,
@@ -639,7 +639,7 @@ wgrad_stream_kernel(const __bf16* __restrict__ a, const __bf16* __restrict__ b, 
   constexpr int TA = 2 * MI * 16, TB = 2 * NI * 16;
   constexpr int SEG_A = TA / 8, SEG_B = TB / 8;
   constexpr int A_BYTES = RPS * TA * 2, B_BYTES = RPS * TB * 2, STAGE = A_BYTES + B_BYTES;
-  constexpr int D = DD ? DD : stream_depth(STAGE), R = D + 1, IDS_R = 2 * D + 1, IDS_BYTES = RPS * 8;
+  constexpr int D = stream_depth(STAGE), R = D + 1, IDS_R = 2 * D + 1, IDS_BYTES = RPS * 8;
   constexpr int IA = SEG_A / 4, IB = SEG_B / 4;
   constexpr int INFLIGHT = (D - 1) * (IA + IB + 1);
   static_assert(INFLIGHT < 64, "vmcnt range");
@@ -919,15 +919,14 @@ template <int MI, int NI>
 int launch_stream(const void* a, const void* b, int64_t n_a, int64_t n_b, const int* spairs, const int* sdesc, int W, int a_col,
                   float* gw, float* partial, int K, int ca, int cb, hipStream_t s) {
   constexpr int TA = 2 * MI * 16, TB = 2 * NI * 16;
-  static const int depth_x = getenv("LIDAL_X_STREAM_DEPTH") ? atoi(getenv("LIDAL_X_STREAM_DEPTH")) : 0;     // (experiments: 2)
-  const int D = depth_x == 2 && 3 * RPS * (TA + TB) * 2 <= 78 * 1024 ? 2 : stream_depth(RPS * (TA + TB) * 2);
-  const size_t lds = (size_t)((D + 1) * RPS * (TA + TB) * 2 + (2 * D + 1) * RPS * 8);
-  auto kern = D == 2 ? wgrad_stream_kernel<MI, NI, 2> : wgrad_stream_kernel<MI, NI, 0>;
-  static size_t attr_set[2][MAX_DEVICES] = {};
+  constexpr int D = stream_depth(RPS * (TA + TB) * 2);
+  constexpr size_t lds = (size_t)((D + 1) * RPS * (TA + TB) * 2 + (2 * D + 1) * RPS * 8);
+  auto kern = wgrad_stream_kernel<MI, NI>;
+  static size_t attr_set[MAX_DEVICES] = {};
   const int dev = current_device();
-  if (attr_set[D == 2][dev] < lds) {
+  if (attr_set[dev] < lds) {
     LIDAL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set[D == 2][dev] = lds;
+    attr_set[dev] = lds;
   }
   const int* soff = sdesc + STREAM_HDR;
   const int* wk = soff + (W + 1);

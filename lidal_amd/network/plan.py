@@ -75,7 +75,7 @@ TRACE = None
 # single scan).  Measured, 3 runs each, same box: 5 scans 16.05 / 16.05 / 16.11 -> 15.42 / 15.39 / 15.38 ms,
 # one scan 7.47 / 7.48 / 7.46 -> 7.01 / 7.82 / 7.02 ms (scripts/exp/side_wgrad.sh).  Same kernels, same results.
 SIDE_ROWS = int(os.environ.get('LIDAL_PLAN_SIDE_ROWS', str(1 << 40)))
-SIDE_MIN_ROWS = int(os.environ.get('LIDAL_PLAN_SIDE_MIN_ROWS', '0'))      # (measured: every threshold above 0 loses, matrix2.sh)
+# (a lower row limit as well was measured, scripts/exp/matrix2.sh: every threshold above 0 loses; not kept)
 # The f32 mode keeps its weight gradients on the MAIN stream (round 6; LIDAL_PLAN_SIDE_F32=1: beside the data gradients).
 # Round 5: one SPVCNN f32 run in ~20 was not bit-reproducible with the fused f64 block tail running while f32 weight gradients
 # ran beside it (gradients differing in the last bits from some layer on; never under bf16).  Round 6, with the weight
@@ -97,15 +97,10 @@ BRANCH_ROWS = int(os.environ.get('LIDAL_PLAN_BRANCH_ROWS', '100000'))
 # hardware queues and the step went from 13.9 to 20.5-21.2 ms, profiles/README.md).  bf16 only (the f32 mode keeps its
 # concurrency as it was, section 5 of DESIGN.md).
 POINT_SIDE = int(os.environ.get('LIDAL_PLAN_POINT_SIDE', '1'))     # 0 = on the main stream, i = on side stream i
-_XJOIN = set(filter(None, os.environ.get('LIDAL_X_JOIN_BEFORE', '').split(',')))
+# f32 mode: a BatchNorm backward never runs beside a weight gradient (_Run._bn_alone).  The bisection switches of that
+# hunt (joins before other operations, split form off per layer kind, scratch from the arena) were removed with their
+# question answered; profiles/README.md, round 6, has what each showed.
 F32_BN_ALONE = os.environ.get('LIDAL_PLAN_F32_BN_ALONE', '1') != '0'
-# experiment switches of the backward plan, read once (a step consulted the environment ~140 times for them: 0.1 ms of a
-# host-bound single-scan step)
-_X_SPLIT_CONV_OFF = os.environ.get('LIDAL_X_SPLIT_CONV') == '0'
-_X_SPLIT_DENSE_OFF = os.environ.get('LIDAL_X_SPLIT_DENSE') == '0'
-_X_STREAMS_MAIN = os.environ.get('LIDAL_X_STREAMS_MAIN') == '1'
-_X_WGRAD_ARENA = os.environ.get('LIDAL_X_WGRAD_ARENA') == '1'
-_X_JOIN_AFTER_WGRAD = os.environ.get('LIDAL_X_JOIN_AFTER_WGRAD') == '1'
 _NARGS = {}
 _HIT_NAMES = {1: 'conv_weight_image', 2: 'conv_apply', 3: 'conv_apply', 4: 'conv_wgrad', 5: 'bn_train_fwd',
               6: 'bn_train_fwd', 7: 'bn_bwd', 8: 'bn_bwd', 9: 'bn_eval_fwd', 10: 'bn_fold', 11: 'colsum',
@@ -744,19 +739,18 @@ class _Run:
         self.nops += 1
         self.open.discard(which)
 
-    def _xjoin(self, what):
-        """The main stream waits for the side streams before an operation of kind `what`.
-        f32 mode, 'bn' (round 6, F32_BN_ALONE): a BatchNorm backward never runs while a weight gradient in the split form
-        is resident beside it -- the one overlap in which the planned f32 step was seen to lose its run-to-run bit-equality
-        (profiles/README.md, round 6: 100 % of the runs with the overlap, 0 of 48 without; neither kernel differs from its
-        solo result when the pair is run in isolation).  LIDAL_X_JOIN_BEFORE=bn,dgrad,tail: the experiment's switches."""
-        if self.open and (what in _XJOIN or (what == 'bn' and F32_BN_ALONE and not self.bf16)):
+    def _bn_alone(self):
+        """The main stream waits for the side streams before a BatchNorm backward of the f32 mode (round 6, F32_BN_ALONE):
+        it never runs while a weight gradient in the split form is resident beside it -- the one overlap in which the
+        planned f32 step was seen to lose its run-to-run bit-equality (profiles/README.md, round 6: 100 % of the runs with
+        the overlap, 0 of 48 without; neither kernel differs from its solo result when the pair is run in isolation)."""
+        if self.open and F32_BN_ALONE and not self.bf16:
             for w_ in sorted(self.open):
                 self.join(w_)
 
     def side(self, rows):
         """Flag of a weight gradient over `rows` rows: side stream 1 (after a fork), or 0 = the main stream."""
-        if not SIDE_ROWS or rows > SIDE_ROWS or rows < SIDE_MIN_ROWS:
+        if not SIDE_ROWS or rows > SIDE_ROWS:
             return 0
         if not self.bf16 and (not SIDE_F32 or _N.TAIL_SUMS_ROWS > 0):
             # (the f32 mode: see SIDE_F32.  The one pair that was ever seen to break run-to-run bit-equality -- the fused
@@ -989,7 +983,7 @@ class _Run:
         p = self.ptr
         c = r.c
         if not flag:
-            self._xjoin('bn')
+            self._bn_alone()
         dx = self.galloc(n * c * self.esz)
         relu = r.relu if relu is None else relu
         if part is not None and part[0]:
@@ -1009,19 +1003,14 @@ class _Run:
         """conv.py conv_backward's wgrad(): gw [k, ci, co] f32 straight into the parameter's gradient slot."""
         ci = c.ci if ci is None else ci
         wcode, slabs = _slabs(n_x, n_g, c.k, ci, c.co, self.dtype)
-        if _X_SPLIT_CONV_OFF and wcode == B.F32_SPLIT:
-            wcode = self.code
-            slabs = int(B.lib_handle().lidal_conv_wgrad_slabs(n_x, n_g, c.k, ci, c.co, wcode))
         flag = self.side(max(n_x, n_g))
         # the streamed form where the level has stream tables (conv.KernelMap.streams_serve: bf16, one channel tile)
         streams = (len(rules) >= 5 and rules[2] and wcode == B.BF16 and not c.transposed and n_x == n_g
                    and _stream_serves(n_x, c.k, ci, c.co))
         if streams:
             slabs = 2 * rules[4]
-            if _X_STREAMS_MAIN:       # (experiment: the streamed launches on the main stream)
-                flag = 0
         nbytes = slabs * ci * c.co * 4 + (c.k * ci * c.co * 4 if ci != c.ci else 0)
-        partial = self.galloc(nbytes) if _X_WGRAD_ARENA else self.scratch(nbytes, flag)
+        partial = self.scratch(nbytes, flag)
         gw = self.slot(c.w)
         if ci != c.ci:                      # the channel-padded stem: gw[:, :ci_w] of the padded gradient
             gw = partial + slabs * ci * c.co * 4
@@ -1035,12 +1024,9 @@ class _Run:
         if ci != c.ci:
             self.w += (OP_COPY2D | flag, gw, ci * c.co * 4, self.slot(c.w), c.ci * c.co * 4, c.k, c.ci * c.co * 4, 0)
             self.nops += 1
-        if _X_JOIN_AFTER_WGRAD and flag:
-            self.join(flag >> 16)
 
     def b_dgrad(self, c, g, n_g, table, n_out, kflip, skip=0, bnb=None):
         """conv.py conv_backward's data gradient: -> (gin [n_out, ci], tile sums or 0)."""
-        self._xjoin('dgrad')
         gin = self.galloc(n_out * c.ci * self.esz)
         wb = _C.apply_workspace_bytes(n_out, c.ci)
         ws = self.scratch(wb) if wb else 0
@@ -1061,13 +1047,10 @@ class _Run:
         gradient per side())."""
         ca, cb = c.ci, cg
         wcode, slabs = _slabs(n, n, 1, ca, cb, self.dtype)
-        if _X_SPLIT_DENSE_OFF and wcode == B.F32_SPLIT:
-            wcode = self.code
-            slabs = int(B.lib_handle().lidal_conv_wgrad_slabs(n, n, 1, ca, cb, wcode))
         direct = linear_slot is None and cb == c.co
         flag = branch or self.side(n)
         nbytes = slabs * ca * cb * 4 + (0 if direct else ca * cb * 4)
-        sc = self.galloc(nbytes) if _X_WGRAD_ARENA else self.scratch(nbytes, flag)
+        sc = self.scratch(nbytes, flag)
         gw = self.slot(c.w) if direct else sc + slabs * ca * cb * 4
         self.w += (OP_CONV_WGRAD | flag, x, g, n, n, 0, self.koff[n], 0, gw, sc, slabs, 1, ca, cb, wcode)
         self.nops += 1
@@ -1106,7 +1089,6 @@ class _Run:
         """blocks._Residual.backward: g [n, co] contiguous -> gx [n, ci]."""
         x, x1, mean1, inv1, y1, x2, mean2, inv2, out, xs, means, invs = self.saved[id(r)]
         co = r.c2.co
-        self._xjoin('tail')
         gm = self.galloc(n * co * self.esz)
         part2 = parts = nb = 0
         sums2 = sumss = nparts = 0

@@ -19,7 +19,7 @@ from .. import backend as B
 
 __all__ = ['FrameBank', 'neighbour_ids', 'score_frame']
 
-# Round 6, measured and NOT adopted (scripts/gpu/r6_check2.sh, 32 frames of 120 k points, nei 10): the queries of a frame taken
+# Round 6, measured and NOT adopted (scripts/gpu/archive/r6_check2.sh, 32 frames of 120 k points, nei 10): the queries of a frame taken
 # in the cell order of its own grid (lidal_interframe_score_ordered: a wave's queries then sit in a handful of neighbouring
 # cells) -- scorer kernels 618 us per frame in scan order, 623 in cell order; frames/s 75.2 / 74.9.  A LiDAR scan is already
 # ordered along its rings, consecutive points ARE neighbours; what the match kernel waits for is the dependent chain bitmap

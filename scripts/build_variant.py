@@ -1,6 +1,6 @@
 """A/B builds of the library: recompile chosen sources with extra -D flags, link with the stock
 objects into scripts/_abl/lib_<name>.so (select it with LIDAL_AMD_LIB=...).
-  python scripts/build_variant.py NAME conv_img.hip -DLIDAL_IMG_G=2 [more sources / flags]"""
+  python scripts/build_variant.py NAME conv_img.hip -DLIDAL_PHASE_STAMPS [more sources / flags]"""
 import os
 import subprocess
 import sys

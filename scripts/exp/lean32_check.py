@@ -1,6 +1,6 @@
 """The bf16 convolution of the layer shapes of the bench batch through lidal_conv_apply_image: time per launch and error
-against an f64 reference on a sample of rows.  Run once per variant (LIDAL_LEAN32=0 / 1, or LIDAL_AMD_LIB=...): the
-selection is read once per process."""
+against an f64 reference on a sample of rows.  Run once per library (the stock one, or a variant build chosen with
+LIDAL_AMD_LIB=...)."""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -31,7 +31,7 @@ while s < 16:
     levels[s * 2] = F.spdownsample(levels[s], 2, 2, s)
     s *= 2
 L = B.lib()
-print('variant: LIDAL_LEAN32=%s LIDAL_AMD_LIB=%s' % (os.environ.get('LIDAL_LEAN32'), os.environ.get('LIDAL_AMD_LIB')))
+print('variant: LIDAL_AMD_LIB=%s' % os.environ.get('LIDAL_AMD_LIB'))
 print('%-30s %10s %12s' % ('layer', 'us', 'err/scale'))
 tot = 0.0
 for stride, ci, co in [(1, 32, 32), (1, 96, 96), (1, 128, 96), (2, 32, 64), (2, 64, 64), (4, 64, 128), (4, 128, 128), (4, 256, 128),

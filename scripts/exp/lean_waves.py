@@ -1,6 +1,6 @@
 """GPU experiment: the lean convolution kernel on every layer shape of the bench batch -- time and a checksum of the
-output -- for A/B builds of the library (LIDAL_AMD_LIB; e.g. scripts/build_variant.py lw16 conv_img.hip
--DLIDAL_LEAN_WAVES=16: 256-row tiles).  The checksums of two builds must agree (bit-equal outputs)."""
+output -- for A/B builds of the library (LIDAL_AMD_LIB; a variant from scripts/build_variant.py).  The checksums of two
+builds must agree (bit-equal outputs)."""
 import hashlib
 import os
 import sys

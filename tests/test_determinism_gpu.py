@@ -60,7 +60,7 @@ def test_fifty_bf16_steps_twice_are_bit_equal_with_every_side_stream_on(name):
     assert plan.ENABLED and plan.SIDE_ROWS and plan.BRANCH_ROWS and plan.POINT_SIDE      # the shipped concurrency
     torch.manual_seed(0)
     base = (SPVCNN if name == 'spvcnn' else MinkUNet)(19).to(DEV).train()
-    batches = _batches(3, 60000)         # 90-107 k voxels: level 0 is above BRANCH_ROWS, every level above SIDE_MIN_ROWS
+    batches = _batches(3, 60000)         # 90-107 k voxels: level 0 is above BRANCH_ROWS, every level's weight gradients on the side stream
     a = _run(base, batches, 50, True, True)
     b = _run(base, batches, 50, True, True)
     _same(a, b)
