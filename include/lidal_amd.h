@@ -119,6 +119,30 @@ int lidal_voxelize_points(const float* points, const float* intensity, int64_t p
                           int64_t* n_out_dev, int32_t* n_invalid_dev, void* ws, int64_t ws_bytes,
                           void* stream);
 
+/* ---- training labels from the round's flags (csrc/labels.hip) ------------------------------------ */
+/* replaces dataset/sk_dataset.py:106-141,170-171 (and dataset/nu_dataset.py:128-160,189-190) for one scan:
+ *   raw         the bytes of the annotation file, u32 [p] (raw_bytes == 4, SemanticKITTI: `labels_anno_p & 0xFFFF`,
+ *               :111, drops the instance id) or u8 [p] (raw_bytes == 1, nuScenes, nu_dataset.py:130)
+ *   label_map   i64 [map_len <= 1024] (:113 `self.label_map[labels_anno_p].astype(np.int64)`); an id >= map_len is an
+ *               IndexError there: here it is counted in *n_invalid_dev and the annotated label reads as 255
+ *   sv_ptr i64 [s+1], sv_idx i64 [nnz], sv_flag i64 [s]: the supervoxel CSR of lidal_segment_entropy and the round's
+ *               flags.  :129-133 `label_anno_mask[p_ids] = False` for each `sv_flag == 1`, `labels_p[label_anno_mask]
+ *               = 255`: a point keeps its label only if at least one flag-1 supervoxel lists it (overlapping lists are
+ *               a union; a point in no list ends at 255).  All three NULL (s = nnz = 0): every point keeps its label
+ *               ('train', 'train_frame', 'val').  A list outside [0, nnz) or an index outside [0, p) is counted in
+ *               *n_invalid_dev and skipped.
+ *   pseudo      i64 [p] or NULL.  :137-141 `labels_p[label_pseudo_mask] = labels_pseudo_p[label_pseudo_mask]`: a point
+ *               listed by at least one flag-2 supervoxel takes pseudo[point], after the mask (it wins where both
+ *               apply).  NULL: flag 2 means nothing ('train_sv').
+ *   unique_idx  i64 [n] or NULL / 0.  :171 `labels_v = labels_p[unique_idxs]` (an index outside [0, p): counted, 255)
+ *   labels_p i64 [p] (16-byte aligned), labels_v i64 [n], n_invalid_dev i32 [1] (set by every call).
+ * No host read.  Workspace: lidal_train_labels_workspace_bytes(p) (two bits per point; unused without flags). */
+int64_t lidal_train_labels_workspace_bytes(int64_t p);
+int lidal_train_labels(const void* raw, int raw_bytes, int64_t p, const int64_t* label_map, int map_len,
+                       const int64_t* sv_ptr, const int64_t* sv_idx, int64_t nnz, int s, const int64_t* sv_flag,
+                       const int64_t* pseudo, const int64_t* unique_idx, int64_t n, int64_t* labels_p,
+                       int64_t* labels_v, int32_t* n_invalid_dev, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- kernel map (rule) building -------------------------------------------------------------- */
 /* replaces the cache-miss branch of F.conv3d (torchsparse/nn/functional/conv.py): kernel_hash +
  * hash_query + nonzero.  `table` was built from sphash(in_coords).

@@ -6,6 +6,11 @@ The random draws stay on the host in the reference's order (`draw_augmentation`)
 numpy generator reproduces the reference's augmentation; everything per point runs in
 lidal_voxelize_points (affine in f64, x20, translation, int cast, unique rows with first-occurrence
 index and inverse map).
+
+Training labels (sk_dataset.py:106-141,170-171; nu_dataset.py:128-160,189-190): `train_labels` turns
+the raw annotation words, the round's supervoxel flags, the supervoxel membership lists and last round's predictions
+into labels_p / labels_v in lidal_train_labels, and `train_sample` composes the three steps into the dict `collate`
+takes.  The frame filters of the loaders (`labeled_frames`, `frames_from_flag`) stay on the host: they pick files.
 """
 import math
 
@@ -15,7 +20,8 @@ import torch
 from . import backend as B
 
 __all__ = ['draw_augmentation', 'voxelize_scan', 'collate', 'parse_calibration', 'parse_poses',
-           'register_scan']
+           'register_scan', 'sk_label_map', 'nu_label_map', 'train_labels', 'train_sample', 'check_labels',
+           'labeled_frames', 'frames_from_flag']
 
 SCALE = 20                # sk_dataset.py:56
 FULL_SCALE = 8192
@@ -85,6 +91,161 @@ def collate(samples):
             'labels_v_b': torch.cat(labels, 0) if labels else None,
             'labels_p_b': torch.cat(labels_p, 0) if labels_p else None,
             'inverse_indices_b': torch.cat(inverse, 0) if inverse else None}
+
+
+# ---- training labels (sk_dataset.py:106-141,170-171) ------------------------------------------
+IGNORE = 255              # train.py:136 ignore_index
+
+# SemanticKITTI (semantic-kitti-api, config/semantic-kitti.yaml): the raw ids of the 19 evaluated classes in the
+# order of the benchmark's class list minus its 'unlabeled' entry, the raw ids the reference leaves out of training,
+# and the moving variants with the static id they fold into.
+_SK_CLASS_IDS = (10, 11, 15, 18, 20, 30, 31, 32, 40, 44, 48, 49, 50, 51, 70, 71, 72, 80, 81)
+_SK_IGNORED_IDS = (0, 1, 13, 16, 52, 60, 99)     # unlabeled, outlier, bus, on-rails, other-structure, lane-marking, other-object
+_SK_MOVING = {252: 10, 253: 31, 254: 30, 255: 32, 256: 16, 257: 13, 258: 18, 259: 20}
+
+# nuScenes-lidarseg: the 32 annotated categories folded into the 16 classes of the lidarseg challenge, by class
+# (barrier, bicycle, bus, car, construction_vehicle, motorcycle, pedestrian, traffic_cone, trailer, truck,
+#  driveable_surface, other_flat, sidewalk, terrain, manmade, vegetation); every other category is ignored.
+_NU_CLASS_IDS = ((9,), (14,), (15, 16), (17,), (18,), (21,), (2, 3, 4, 6), (12,), (22,), (23,), (24,), (25,), (26,), (27,),
+                 (28,), (30,))
+
+
+def sk_label_map():
+    """i64 [260]: raw SemanticKITTI id -> training class 0..18 or 255, the table sk_dataset.py:66-92 builds.  An id
+    the dataset does not define maps to class 0, not to 255: the reference's table starts as np.zeros(260)."""
+    table = np.zeros(260, dtype=np.int64)
+    for raw in _SK_IGNORED_IDS:
+        table[raw] = IGNORE
+    for cls, raw in enumerate(_SK_CLASS_IDS):
+        table[raw] = cls
+    for raw, static in _SK_MOVING.items():
+        table[raw] = table[static]
+    return table
+
+
+def nu_label_map():
+    """i64 [100]: nuScenes-lidarseg category -> training class 0..15 or 255 (nu_dataset.py:111-113)."""
+    table = np.full(100, IGNORE, dtype=np.int64)
+    for cls, raws in enumerate(_NU_CLASS_IDS):
+        for raw in raws:
+            table[raw] = cls
+    return table
+
+
+def _to_i64(x, dev):
+    """A host array or a tensor of any integer / bool type -> i64 on dev (round-0 flag files hold bool,
+    sk_dataloader.py:115-118)."""
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x)).astype(np.int64))
+    return x.to(device=dev, dtype=torch.int64).contiguous()
+
+
+def train_labels(raw_labels, label_map, sv_csr=None, sv_flag=None, pseudo=None, unique_idxs=None, check=True):
+    """sk_dataset.py:106-141,170-171 / nu_dataset.py:128-160,189-190 for one scan, on the GPU.
+      raw_labels   the annotation file as a GPU tensor: uint8 [P] (nuScenes) or int32 / uint32 [P] holding the u32
+                   words of a SemanticKITTI .label file (lidal_amd.io.load_labels returns either)
+      label_map    i64 table (sk_label_map() / nu_label_map(); a host array is uploaded)
+      sv_csr       (sv_ptr i64 [S+1], sv_idx i64) on the GPU (lidal_amd.score.interframe.sv_csr; a third element is ignored) and
+      sv_flag      [S] in {0, 1, 2} (any integer or bool type, host or GPU): the modes 'train_sv' and, with
+      pseudo       i64 [P] last round's predictions, 'train_sv_pseudo'.  Without flags every point keeps its label
+                   ('train', 'train_frame', 'val').
+      unique_idxs  i64 [N] of voxelize_scan, or None for labels_p alone ('val').
+    Returns (labels_p i64 [P], labels_v i64 [N] or None).  A raw id beyond the table (numpy's IndexError in the
+    reference) or an index outside its array raises; check=False skips that read-back -- the only synchronisation here
+    -- and returns (labels_p, labels_v, n_invalid i32 [1] on the GPU) for check_labels to look at later."""
+    B.require_gpu(raw_labels)
+    dev = raw_labels.device
+    if raw_labels.dtype == torch.uint8:
+        raw_bytes = 1
+    elif raw_labels.dtype in (torch.int32, getattr(torch, 'uint32', torch.int32)):
+        raw_bytes = 4
+    else:
+        raise TypeError('raw_labels must be uint8 (nuScenes) or int32 / uint32 (SemanticKITTI), not %s' % raw_labels.dtype)
+    raw_labels = raw_labels.contiguous().reshape(-1)
+    p = raw_labels.shape[0]
+    label_map = _to_i64(label_map, dev)
+    if (sv_csr is None) != (sv_flag is None):
+        raise ValueError('sv_csr and sv_flag come together')
+    sv_ptr = sv_idx = flags = None
+    s = nnz = 0
+    if sv_flag is not None:
+        sv_ptr, sv_idx = _to_i64(sv_csr[0], dev), _to_i64(sv_csr[1], dev)
+        flags = _to_i64(sv_flag, dev)
+        s, nnz = flags.shape[0], sv_idx.shape[0]
+        if sv_ptr.shape[0] != s + 1:
+            raise ValueError('%d flags for %d supervoxels' % (s, sv_ptr.shape[0] - 1))
+        if s == 0:                       # an empty tensor has no address: flags present, none set
+            flags = torch.zeros(1, dtype=torch.int64, device=dev)
+        B.require_gpu(sv_ptr, sv_idx, flags)
+    if pseudo is not None:
+        B.require_gpu(pseudo)
+        pseudo = pseudo.to(torch.int64).contiguous()
+        assert pseudo.shape[0] == p                                  # sk_dataset.py:120
+    n = 0
+    labels_v = None
+    if unique_idxs is not None:
+        B.require_gpu(unique_idxs)
+        unique_idxs = unique_idxs.to(torch.int64).contiguous()
+        n = unique_idxs.shape[0]
+        labels_v = B.empty(n, torch.int64, dev)
+    labels_p = B.empty(p, torch.int64, dev)
+    n_invalid = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = B.lib().lidal_train_labels_workspace_bytes(p)
+    ws = B.workspace(ws_bytes, dev)
+    B.check(B.lib().lidal_train_labels(B.ptr(raw_labels), raw_bytes, p, B.ptr(label_map), label_map.shape[0],
+                                       B.ptr(sv_ptr), B.ptr(sv_idx) if nnz else None, nnz, s, B.ptr(flags),
+                                       B.ptr(pseudo), B.ptr(unique_idxs) if n else None, n, B.ptr(labels_p),
+                                       B.ptr(labels_v) if n else None, B.ptr(n_invalid), B.ptr(ws), ws_bytes,
+                                       B.stream()), 'train_labels')
+    if not check:
+        return labels_p, labels_v, n_invalid
+    check_labels(n_invalid)
+    return labels_p, labels_v
+
+
+def check_labels(n_invalid):
+    """Raises if any of the counters (an i32 [1] GPU tensor of train_labels(check=False), a sample of
+    train_sample(check=False), or a list of either) is not zero.  One read-back for all of them."""
+    items = n_invalid if isinstance(n_invalid, (list, tuple)) else [n_invalid]
+    counters = [c['labels_invalid'] if isinstance(c, dict) else c for c in items]
+    if not counters:
+        return
+    bad = int(torch.stack([c.reshape(()) for c in counters]).sum().item())
+    if bad != 0:
+        raise IndexError('train_labels: %d raw label ids beyond the label table or indices outside their array' % bad)
+
+
+def train_sample(points, intensity, raw_labels, label_map, sv_csr=None, sv_flag=None, pseudo=None, rng=np.random,
+                 scale=SCALE, full_scale=FULL_SCALE, check=True):
+    """One training __getitem__ (sk_dataset.py:98-178) on the GPU: draw_augmentation(rng), voxelize_scan and
+    train_labels -> {'coords_v', 'feats_v', 'labels_v'}, the sample `collate` takes; collate(...) of the
+    batch's samples is what train_step takes.  check=False leaves the invalid-id counter in the sample
+    ('labels_invalid', ignored by collate) for one check_labels(samples) per batch."""
+    trans_m, rnd = draw_augmentation(rng)
+    coords_v, feats_v, uniq, _ = voxelize_scan(points, intensity, trans_m, rnd, scale, full_scale)
+    out = train_labels(raw_labels, label_map, sv_csr, sv_flag, pseudo, uniq, check=check)
+    sample = {'coords_v': coords_v, 'feats_v': feats_v, 'labels_v': out[1]}
+    if not check:
+        sample['labels_invalid'] = out[2]
+    return sample
+
+
+def labeled_frames(sv_flags_per_frame):
+    """sk_dataloader.py:279-290: the indices of the frames with at least one flagged supervoxel (`flag.sum() != 0`;
+    a frame with pseudo-labeled supervoxels only counts, as there).  Host arrays in, i64 indices out."""
+    return np.array([i for i, flag in enumerate(sv_flags_per_frame) if np.asarray(flag).sum() != 0], dtype=np.int64)
+
+
+def frames_from_flag(frame_flag):
+    """sk_dataloader.py:160-172: frame flags (one array, or one per sequence in sequence order) -> the indices of the
+    selected frames in the concatenated frame list."""
+    if isinstance(frame_flag, (list, tuple)):
+        flat = np.array([])
+        for f in frame_flag:
+            flat = np.append(flat, np.asarray(f))
+    else:
+        flat = np.asarray(frame_flag).reshape(-1)
+    return np.nonzero(flat.astype(bool))[0].astype(np.int64)
 
 
 # ---- world-frame registration (dataset/prepare_kdtree_sk.py, SURVEY.md 8f-2) ---------------------

@@ -15,6 +15,11 @@ vice versa.
   boundary/<seq>/<frame>.npy   f32 [P]       the surface variation of a raw scan
                                dataset/ReDAL/gen_surface_variation_sk.py -> ReDAL.py:57
   <dir>/current.pt             {'model_state_dict', 'iteration', 'ep_id'}   train.py:151-155
+  sequences/<seq>/velodyne/<frame>.bin   f32 [P, 4] (x, y, z, intensity)      dataset/sk_dataset.py:101
+  samples/LIDAR_TOP/<token>.pcd.bin      f32 [P, 5], the first 4 used         dataset/nu_dataset.py:122-123
+  sequences/<seq>/labels/<frame>.label   u32 [P], class in the low 16 bits    dataset/sk_dataset.py:108-111
+  lidarseg/.../<token>_lidarseg.bin      u8 [P]                               dataset/nu_dataset.py:130
+  pred/.../<frame>.npy (read back as pseudo labels)   i64 [P]                 dataset/sk_dataset.py:119
 """
 import os
 import pickle
@@ -24,7 +29,7 @@ import torch
 
 __all__ = ['save_prob_pred', 'load_prob', 'load_supervoxels', 'save_supervoxels', 'load_sv_flag',
            'save_sv_flag', 'load_sv_stats', 'save_sv_stats', 'load_curvature', 'save_curvature', 'frame_flag_path', 'load_frame_flag',
-           'save_frame_flag', 'save_checkpoint', 'load_checkpoint']
+           'save_frame_flag', 'save_checkpoint', 'load_checkpoint', 'load_scan', 'load_labels', 'load_pred']
 
 
 def _mkdir_for(path):
@@ -99,6 +104,45 @@ def save_curvature(path, curvature):
     curvature = curvature.detach().cpu().numpy() if torch.is_tensor(curvature) else np.asarray(curvature)
     _mkdir_for(path)
     np.save(path, curvature.astype(np.float32, copy=False))
+
+
+def _dataset_kind(dataset):
+    kind = str(dataset).upper()
+    if kind in ('SK', 'SEMANTICKITTI'):
+        return 'SK'
+    if kind in ('NU', 'NUSCENES'):
+        return 'NU'
+    raise ValueError("dataset must be 'SK' or 'NU', not %r" % (dataset,))
+
+
+def load_scan(path, dataset, device=None):
+    """A LiDAR sweep -> (points f32 [P,3], intensity f32 [P]): 4 floats per point for SemanticKITTI
+    (sk_dataset.py:101), 5 per point with the first 4 used for nuScenes (nu_dataset.py:122-123)."""
+    width = 4 if _dataset_kind(dataset) == 'SK' else 5
+    raw = np.fromfile(path, dtype=np.float32).reshape(-1, width)
+    points = torch.from_numpy(np.ascontiguousarray(raw[:, :3]))
+    intensity = torch.from_numpy(np.ascontiguousarray(raw[:, 3]))
+    return (points.to(device), intensity.to(device)) if device is not None else (points, intensity)
+
+
+def load_labels(path, dataset, device=None):
+    """An annotation file as lidal_amd.data.train_labels takes it: SemanticKITTI u32 [P] (sk_dataset.py:108-109) as an
+    int32 tensor of the same bits (instance id in the high half, masked on the device), nuScenes u8 [P]
+    (nu_dataset.py:130) as a uint8 tensor."""
+    if _dataset_kind(dataset) == 'SK':
+        t = torch.from_numpy(np.fromfile(path, dtype=np.uint32).reshape(-1).view(np.int32))
+    else:
+        t = torch.from_numpy(np.fromfile(path, dtype=np.uint8).reshape(-1))
+    return t.to(device) if device is not None else t
+
+
+def load_pred(path, device=None):
+    """pred/.../<frame>.npy of save_prob_pred -> i64 [P], last round's predictions (the pseudo labels of
+    sk_dataset.py:119)."""
+    pred = np.load(path)
+    assert pred.ndim == 1 and pred.dtype.kind in 'iu', (pred.dtype, pred.shape)
+    t = torch.from_numpy(pred.astype(np.int64, copy=False))
+    return t.to(device) if device is not None else t
 
 
 def frame_flag_path(root, dataset_name, seq, r_id, metric=None, model_name=None):
