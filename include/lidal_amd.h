@@ -551,7 +551,13 @@ int lidal_register_points(const float* points, int64_t p, const double* pose_dev
  * pickled sklearn KDTree of dataset/prepare_kdtree_sk.py:83 as used by
  * score/sv_level/LiDAL.py:52-66).  cell: any size > 0 (kept in the grid; a query visits the cells that meet the cube of
  * its match radius: 27 for cell = radius, at most 8 for cell = 2 x radius -- the answers are the same).
- *   pts f64 [p,3];  grid bytes from lidal_nn_grid_bytes(p). */
+ *   pts f64 [p,3];  grid bytes from lidal_nn_grid_bytes(p).
+ * Key range: a cell index is packed into 21 bits per axis, so a coordinate v is IN RANGE iff floor(v / cell) lies in
+ * [-(2^20 - 1), 2^20 - 1] (209 km either side of the origin at cell = 0.2 m).  A point with a coordinate that is NaN,
+ * +-Inf or out of range is filed in a parking cell that no in-range query probes; a query with such a coordinate, or
+ * whose cube [q - r, q + r]^3 leaves the range, matches nothing.  So such a point matches nothing and is matched by
+ * nothing: map_count = 0, interd = 0, intere = the entropy of its own probability row.  Decided per point on the device
+ * (no host check, no synchronisation); every other point of the frame is scored as if it were absent. */
 int64_t lidal_nn_grid_bytes(int64_t p);
 int64_t lidal_nn_grid_workspace_bytes(int64_t p);
 int lidal_nn_grid_build(const double* pts, int64_t p, double cell, void* grid, int64_t grid_bytes,

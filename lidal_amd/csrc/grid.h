@@ -36,6 +36,19 @@ __host__ __device__ inline int64_t grid_off_bits(int64_t cap, int64_t q) { retur
 
 constexpr int64_t kBias = 1 << 20;
 
+// The key range.  A cell index is IN RANGE iff floor(v / cell), as a double, lies in [-(2^20 - 1), 2^20 - 1]: it then
+// fits its 21-bit field of cell_key with field value >= 1.  Written so that NaN fails (and +-Inf, and anything a cast
+// to int64_t could not hold): the test is made on the double, BEFORE any cast.
+constexpr int64_t kCellMax = kBias - 1;
+__host__ __device__ inline bool cell_in_range(double f) { return f >= -(double)kCellMax && f <= (double)kCellMax; }
+// The cell index of coordinate v, or -2^20 (field value 0: the PARKING cell of that axis) when v is out of range.
+// The build files an out-of-range point there; a query whose probed cube is in range never forms a key with a zero
+// field, so a parked point is a candidate of nobody.
+__host__ __device__ inline int64_t cell_index(double v, double cell) {
+  const double f = floor(v / cell);
+  return cell_in_range(f) ? (int64_t)f : -kBias;
+}
+
 __device__ __forceinline__ uint64_t cell_key(int64_t ix, int64_t iy, int64_t iz) {
   return ((uint64_t)(ix + kBias) << 42) | ((uint64_t)(iy + kBias) << 21) | (uint64_t)(iz + kBias);
 }

@@ -153,9 +153,8 @@ __global__ void __launch_bounds__(256) grid_keys_kernel(const double* __restrict
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p) return;
   if (i == 0) { hdr->p = p; hdr->cap = 0; hdr->cell = cell; hdr->inv_cell_unused = 0.; }     // the queries read the cell size
-  int64_t ix = (int64_t)floor(pts[i * 3 + 0] / cell), iy = (int64_t)floor(pts[i * 3 + 1] / cell),
-          iz = (int64_t)floor(pts[i * 3 + 2] / cell);
-  keys[i] = cell_key(ix, iy, iz);
+  // (a coordinate that is NaN, +-Inf or beyond 2^20 cells goes to the parking cell of its axis: grid.h)
+  keys[i] = cell_key(cell_index(pts[i * 3 + 0], cell), cell_index(pts[i * 3 + 1], cell), cell_index(pts[i * 3 + 2], cell));
   idx[i] = (int)i;
 }
 
@@ -205,11 +204,19 @@ __device__ __forceinline__ void grid_scan_cell(const GridView& g, uint64_t key, 
 __device__ __forceinline__ int grid_nearest(const GridView& g, const double* __restrict__ npts,
                                             double qx, double qy, double qz, double r, double* d2out) {
   const double rr = r * (1.0 + 1e-9) + 1e-12;            // (a point at exactly r must not fall off the cube through rounding)
-  const int64_t x0 = (int64_t)floor((qx - rr) / g.cell), x1 = (int64_t)floor((qx + rr) / g.cell);
-  const int64_t y0 = (int64_t)floor((qy - rr) / g.cell), y1 = (int64_t)floor((qy + rr) / g.cell);
-  const int64_t z0 = (int64_t)floor((qz - rr) / g.cell), z1 = (int64_t)floor((qz + rr) / g.cell);
+  const double fx0 = floor((qx - rr) / g.cell), fx1 = floor((qx + rr) / g.cell);
+  const double fy0 = floor((qy - rr) / g.cell), fy1 = floor((qy + rr) / g.cell);
+  const double fz0 = floor((qz - rr) / g.cell), fz1 = floor((qz + rr) / g.cell);
   double best = INFINITY;
   int arg = -1;
+  // a query that is NaN, +-Inf or whose cube leaves the key range matches nothing: told on the doubles, before any cast
+  // (a saturated bound would make the loops below endless)
+  if (!(cell_in_range(fx0) && cell_in_range(fx1) && cell_in_range(fy0) && cell_in_range(fy1) && cell_in_range(fz0) &&
+        cell_in_range(fz1))) {
+    *d2out = best;
+    return arg;
+  }
+  const int64_t x0 = (int64_t)fx0, x1 = (int64_t)fx1, y0 = (int64_t)fy0, y1 = (int64_t)fy1, z0 = (int64_t)fz0, z1 = (int64_t)fz1;
   // (round 5, measured: probing the eight cells of a query in stages -- eight bitmap words, then the slots, then the values,
   // each stage's loads in flight together -- 287.8 us against this loop's 289.1: the kernel is bound by the ~20 random
   // 64-byte sectors a query touches beyond the L2s, 1.5 GB per launch, not by a thread's dependent chain)

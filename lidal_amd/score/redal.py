@@ -31,22 +31,32 @@ FT_DIM = 96            # ReDAL.py:22
 KNN_CELL = 0.5         # search grid cell (metres); the neighbours do not depend on it, only the search time does
 
 
-def _xyz(xyz):
+GRID_CELLS = 2 ** 20 - 1        # csrc/grid.h: cell indices beyond +-GRID_CELLS are outside the grid's key range
+
+
+def _xyz(xyz, cell):
     if not torch.is_tensor(xyz):
         xyz = torch.from_numpy(np.ascontiguousarray(xyz, dtype=np.float32)).cuda()
     B.require_gpu(xyz)
     xyz = xyz.float().contiguous()
     assert xyz.ndim == 2 and xyz.shape[1] == 3, tuple(xyz.shape)
-    if not bool(torch.isfinite(xyz).all()):
+    if xyz.shape[0] == 0:
+        return xyz
+    reach = float(xyz.abs().max())          # (NaN if any coordinate is; the one synchronisation of this check)
+    if not reach < float('inf'):
         # a NaN query never fills its list and searches until its ring covers the scan's cell box
         raise ValueError('knn / surface_variation: the coordinates must be finite (NaN or inf found)')
+    if not reach < (GRID_CELLS - 1) * float(cell):
+        # the grid build parks such a point in a cell no query forms a key for: the search would silently miss it
+        raise ValueError('knn / surface_variation: a coordinate of magnitude %g is outside the search grid '
+                         '(%d cells of %g)' % (reach, GRID_CELLS, float(cell)))
     return xyz
 
 
 def knn(xyz, k, cell=KNN_CELL):
     """The k nearest OTHER points of every point of xyz (f32 [P,3]): i32 [P,k] device tensor, sorted by distance, ties
     to the lower index.  P < k + 1 raises (the reference would index out of range)."""
-    xyz = _xyz(xyz)
+    xyz = _xyz(xyz, cell)
     p = xyz.shape[0]
     out = torch.empty((p, k), dtype=torch.int32, device=xyz.device)
     nbytes = B.lib().lidal_knn_workspace_bytes(p)
@@ -58,7 +68,7 @@ def knn(xyz, k, cell=KNN_CELL):
 def surface_variation(xyz, k=50, threshold=0.1, cell=KNN_CELL):
     """gen_surface_variation_sk.py::boundary_extractor(xyz, threshold=0.1) with k_n = 50: f32 [P] device tensor.
     threshold=None leaves sigma unclipped."""
-    xyz = _xyz(xyz)
+    xyz = _xyz(xyz, cell)
     p = xyz.shape[0]
     out = torch.empty(p, dtype=torch.float32, device=xyz.device)
     nbytes = B.lib().lidal_knn_workspace_bytes(p)

@@ -208,6 +208,19 @@ def test_knn_refusals():
                 f(_t(pts))
 
 
+def test_knn_refuses_points_outside_the_search_grid():
+    """A finite coordinate beyond 2^20 cells: the grid build parks it where no query looks (csrc/grid.h), so the wrapper
+    refuses it instead of returning lists that silently lack it."""
+    from lidal_amd.score import knn, surface_variation
+    pts = np.random.RandomState(46).uniform(0, 1, size=(100, 3)).astype(np.float32)
+    far = pts.copy()
+    far[37, 2] = -6e5                                   # 1.2e6 cells of 0.5
+    for f in (lambda a: knn(a, 10), lambda a: surface_variation(a), lambda a: knn(a, 10, cell=0.5)):
+        with pytest.raises(ValueError, match='outside the search grid'):
+            f(_t(far))
+    assert np.array_equal(knn(_t(pts), 10).cpu().numpy(), redal_ref.knn_brute(pts, 10))      # a valid call after the refusals
+
+
 # ------------------------------------------------------------------------------------------------ surface variation
 def _sigma(xyz, k=50, threshold=0.1):
     from lidal_amd.score import surface_variation
