@@ -60,7 +60,8 @@ int lidal_kernel_hash(const int32_t* coords, int64_t n, const int32_t* offsets, 
 
 /* replaces backend.hash_query_cuda  (F.sphashquery: network/utils.py:19,48,76).
  * Open-addressing table of 64-bit keys in HBM; value = index of the FIRST occurrence of the key
- * (the CPU dense_hash_map::insert semantics).  Keys must be < 2^63 (sphash output is 60 bit).
+ * (the CPU dense_hash_map::insert semantics).  Any i64 key is allowed: the all-ones key (-1), which marks an empty
+ * slot, is kept in the header instead of a slot and found like any other.
  * The buffer holds cap = 2^k >= 2 n slots {key u64 | value i32} and an occupancy bitmap of 8 bits per slot that the
  * kernel-map probes test before they touch a slot (most probed neighbours do not exist), a second, SPATIAL bitmap of the
  * same size (x-contiguous, direct mapped: the three x-neighbours of a voxel in one word) and a 64-byte header. */
@@ -80,14 +81,16 @@ int lidal_hash_table_query(const void* table, int64_t table_bytes, const int64_t
 
 /* ---- sorted unique / downsample ------------------------------------------------------------- */
 /* replaces torch.unique(pc_hash) in network/utils.py:18 (sorted unique of i64 keys).
- * out [n] capacity; n_out_dev i64[1]. */
+ * out [n] capacity; n_out_dev i64[1].  Keys are 0 <= key < 2^63 (sphash output is 60 bit); a negative key is reported
+ * as *n_out_dev = -1 (no other output is valid then). */
 int64_t lidal_unique_workspace_bytes(int64_t n);
 int lidal_unique_sorted_i64(const int64_t* keys, int64_t n, int64_t* out, int64_t* n_out_dev,
                             void* ws, int64_t ws_bytes, void* stream);
 /* replaces F.spdownsample (torchsparse/nn/functional/downsample.py; reached from the four
  * stride-2 convs, network/spvcnn.py:28,34,40,46): xyz floored to multiples of `sample_stride`
  * (= conv stride x tensor stride), unique rows sorted by (batch,x,y,z).
- * Requires 0 <= x,y,z < 65536 and 0 <= batch < 32768.  out i32 [n,4] capacity. */
+ * Requires 0 <= x,y,z < 65536 and 0 <= batch < 32768; a row outside these ranges is reported as *n_out_dev = -1 (no
+ * other output is valid then).  out i32 [n,4] capacity. */
 int64_t lidal_downsample_workspace_bytes(int64_t n);
 int lidal_downsample(const int32_t* coords, int64_t n, int sx, int sy, int sz, int32_t* out,
                      int64_t* n_out_dev, void* ws, int64_t ws_bytes, void* stream);
@@ -170,9 +173,10 @@ int lidal_kmap_build(const void* table, int64_t table_bytes, const int32_t* out_
 int lidal_kmap_from_rules(const int32_t* nbmaps, const int32_t* nbsizes, int k, int64_t n_rules,
                           int64_t n_in, int64_t n_out, int32_t* nbr_out, int32_t* n_bad_dev, void* stream);
 /* All kernel maps of a network in one chain of launches (n_jobs <= 12; HOST arrays of length n_jobs holding,
- * per map, the arguments of lidal_kmap_build; nbmaps[j] == NULL: neighbour table only): every stage (fill,
+ * per map, the arguments of lidal_kmap_build; nbsizes[j] == NULL: neighbour table only): every stage (fill,
  * probe, count, scan, compact, sizes) is one launch over all maps.  Results per map are those of
- * lidal_kmap_build.  ws >= lidal_kmap_build_batch_workspace_bytes(n_out, k, n_jobs). */
+ * lidal_kmap_build, an empty level (n_out[j] == 0: nbsizes and koff all zero) and every kernel volume it takes
+ * (k <= 1023) included.  ws >= lidal_kmap_build_batch_workspace_bytes(n_out, k, n_jobs). */
 int64_t lidal_kmap_build_batch_workspace_bytes(const int64_t* n_out, const int32_t* k, int n_jobs);
 int lidal_kmap_build_batch(const void* const* tables, const int64_t* table_bytes,
                            const int32_t* const* out_coords, const int64_t* n_out,

@@ -61,6 +61,11 @@ __device__ __forceinline__ int64_t fnv60(int32_t x, int32_t y, int32_t z, int32_
 // resolved by the slots as before).  Same results by construction.  A view without a bitmap (bits == NULL: the
 // scorer's cell tables, tables of the old 12-byte size) skips the test.
 constexpr uint64_t kEmptyKey = 0xFFFFFFFFFFFFFFFFULL;
+// The all-ones key is the empty mark of a slot, so it cannot live in one: a table with a header keeps it there instead
+// (hdr[kAllOnesWord] = kAllOnesBase - first index, 0: absent), and table_lookup answers it from that word.  A bare
+// table (no header) does not hold it: the key is absent there.
+constexpr int kAllOnesWord = 4;
+constexpr int kAllOnesBase = 0x7FFFFFFF;
 
 struct TableView {
   unsigned long long* keys;
@@ -132,6 +137,10 @@ __device__ __forceinline__ unsigned sbit_of(int x, int y, int z, int b, int shif
 }
 
 __device__ __forceinline__ int table_lookup(const TableView& t, uint64_t key) {
+  if (key == kEmptyKey) {                    // never in a slot (it would read as an empty one): see kAllOnesWord
+    const int v = t.hdr != nullptr ? t.hdr[kAllOnesWord] : 0;
+    return v > 0 ? kAllOnesBase - v : -1;
+  }
   uint64_t s = slot_of(key, t.mask);
   while (true) {
     unsigned long long k = t.keys[s];

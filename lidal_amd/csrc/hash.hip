@@ -39,6 +39,10 @@ __global__ void __launch_bounds__(256) table_insert_kernel(const int64_t* __rest
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += stride) {
     uint64_t key = (uint64_t)keys[i];
+    if (key == kEmptyKey) {                  // the empty mark itself: kept in the header (common.h), first index wins
+      if (t.hdr != nullptr) atomicMax(const_cast<int*>(&t.hdr[kAllOnesWord]), kAllOnesBase - (int)i);
+      continue;
+    }
     const uint64_t mixed = mix_key(key);
     uint64_t s = mixed & t.mask;
     if (t.bits != nullptr) {

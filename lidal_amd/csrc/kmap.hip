@@ -99,7 +99,8 @@ __global__ void __launch_bounds__(kBlock) head_compact_kernel(const uint64_t* __
                                                               const int64_t* __restrict__ offsets,
                                                               int64_t nblocks,
                                                               int64_t* __restrict__ out,
-                                                              int64_t* __restrict__ n_out) {
+                                                              int64_t* __restrict__ n_out,
+                                                              const int* __restrict__ bad, int signed_keys) {
   __shared__ int wave_cnt[kBlock / 64];
   int64_t base = (int64_t)blockIdx.x * kTile;
   int64_t pos = offsets[blockIdx.x];
@@ -113,7 +114,10 @@ __global__ void __launch_bounds__(kBlock) head_compact_kernel(const uint64_t* __
     if (head) out[pos + r] = (int64_t)v;
     pos += tot;
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0) *n_out = offsets[nblocks];
+  // input the caller must refuse is reported with the count it reads back anyway, as -1: a row flagged by the kernel that
+  // made the keys (`bad`), or -- keys taken as signed, sorted as unsigned: the largest is last -- a negative key
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    *n_out = ((bad != nullptr && *bad) || (signed_keys && (s[n - 1] >> 63))) ? -1 : offsets[nblocks];
 }
 
 struct UniqueWs {
@@ -141,7 +145,7 @@ UniqueWs carve_unique_ws(void* ws, int64_t n) {
 }
 
 int unique_sorted_u64(const uint64_t* keys, int64_t n, int64_t* out, int64_t* n_out_dev, void* ws,
-                      int64_t ws_bytes, int end_bit, hipStream_t s) {
+                      int64_t ws_bytes, int end_bit, hipStream_t s, const int* bad = nullptr, int signed_keys = 0) {
   if (n == 0) {
     LIDAL_HIP(hipMemsetAsync(n_out_dev, 0, 8, s));
     return 0;
@@ -157,7 +161,7 @@ int unique_sorted_u64(const uint64_t* keys, int64_t n, int64_t* out, int64_t* n_
   scan_counts_kernel<<<1, 1024, 0, s>>>(u.counts, nblocks, u.offsets);
   LIDAL_CHECK_LAUNCH("scan_counts");
   head_compact_kernel<<<(int)nblocks, kBlock, 0, s>>>(u.sorted, n, u.offsets, nblocks, out,
-                                                       n_out_dev);
+                                                       n_out_dev, bad, signed_keys);
   LIDAL_CHECK_LAUNCH("head_compact");
   return 0;
 }
@@ -165,11 +169,14 @@ int unique_sorted_u64(const uint64_t* keys, int64_t n, int64_t* out, int64_t* n_
 // ---------------- downsample: pack (b,x,y,z) -> u64, unique, unpack ----------------
 __global__ void __launch_bounds__(256) pack_coords_kernel(const int4* __restrict__ coords,
                                                           int64_t n, int sx, int sy, int sz,
-                                                          uint64_t* __restrict__ keys) {
+                                                          uint64_t* __restrict__ keys, int* __restrict__ bad) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int4 c = coords[i];
-  // floor division: coordinates are non-negative on this path (checked by the caller)
+  // the key has 16 bits per coordinate and 15 for the batch index (63 sorted bits): anything else -- a negative value
+  // included -- would spill into its neighbours, so it is flagged and lidal_downsample reports it
+  if (((unsigned)c.x | (unsigned)c.y | (unsigned)c.z) >> 16 || (unsigned)c.w >> 15) *bad = 1;
+  // floor division: the coordinates that pass are non-negative
   uint64_t x = (uint64_t)((c.x / sx) * sx), y = (uint64_t)((c.y / sy) * sy),
            z = (uint64_t)((c.z / sz) * sz), b = (uint64_t)c.w;
   keys[i] = (b << 48) | (x << 32) | (y << 16) | z;
@@ -673,7 +680,7 @@ extern "C" int lidal_unique_sorted_i64(const int64_t* keys, int64_t n, int64_t* 
                                        int64_t* n_out_dev, void* ws, int64_t ws_bytes,
                                        void* stream) {
   return unique_sorted_u64((const uint64_t*)keys, n, out, n_out_dev, ws, ws_bytes, 64,
-                           (hipStream_t)stream);
+                           (hipStream_t)stream, nullptr, 1);
 }
 
 extern "C" int lidal_downsample(const int32_t* coords, int64_t n, int sx, int sy, int sz,
@@ -693,9 +700,11 @@ extern "C" int lidal_downsample(const int32_t* coords, int64_t n, int sx, int sy
   uint64_t* packed = (uint64_t*)ws;
   int64_t* uniq = (int64_t*)((char*)ws + kb);
   void* uws = (char*)ws + 2 * kb;
-  pack_coords_kernel<<<(int)cdiv(n, 256), 256, 0, s>>>((const int4*)coords, n, sx, sy, sz, packed);
+  int* bad = (int*)((char*)ws + need - 256);                 // (the slack at the end of the unique workspace)
+  LIDAL_HIP(hipMemsetAsync(bad, 0, 4, s));
+  pack_coords_kernel<<<(int)cdiv(n, 256), 256, 0, s>>>((const int4*)coords, n, sx, sy, sz, packed, bad);
   LIDAL_CHECK_LAUNCH("pack_coords");
-  int rc = unique_sorted_u64(packed, n, uniq, n_out_dev, uws, ws_bytes - 2 * kb, 63, s);
+  int rc = unique_sorted_u64(packed, n, uniq, n_out_dev, uws, ws_bytes - 2 * kb, 63, s, bad);
   if (rc) return rc;
   unpack_coords_kernel<<<(int)cdiv(n, 256), 256, 0, s>>>(uniq, n_out_dev, (int4*)out);
   LIDAL_CHECK_LAUNCH("unpack_coords");
@@ -967,7 +976,7 @@ __global__ void __launch_bounds__(kBlock) kmap_compact_batch_kernel(KmapBatch b)
   kmap_compact_body(b.nbr[j], b.n_out[j], (const int64_t*)b.offs[j], b.nblocks[j], b.nbmaps[j], l % b.nblocks[j],
                     (int)(l / b.nblocks[j]));
 }
-__global__ void __launch_bounds__(64) kmap_sizes_batch_kernel(KmapBatch b) {
+__global__ void __launch_bounds__(1024) kmap_sizes_batch_kernel(KmapBatch b) {
   const int j = blockIdx.x, k = threadIdx.x, K = b.k[j];
   if (!b.rules[j]) return;
   const long long* offsets = b.offs[j];
@@ -987,7 +996,9 @@ extern "C" int64_t lidal_kmap_build_batch_workspace_bytes(const int64_t* n_out, 
   return total;
 }
 
-// Host arrays of length n_jobs (<= 12): the arguments of lidal_kmap_build per map.  nbmaps[j] == NULL: table only.
+// Host arrays of length n_jobs (<= 12): the arguments of lidal_kmap_build per map.  nbsizes[j] == NULL: table only.
+// A map without output rows (n_out[j] == 0: an empty level) takes no block of any launch and gets the empty map of
+// lidal_kmap_build: nbsizes and koff all zero.
 extern "C" int lidal_kmap_build_batch(const void* const* tables, const int64_t* table_bytes,
                                       const int32_t* const* out_coords, const int64_t* n_out,
                                       const int32_t* const* offsets, const int32_t* k, const int32_t* symmetric,
@@ -1003,16 +1014,18 @@ extern "C" int lidal_kmap_build_batch(const void* const* tables, const int64_t* 
   char* w = (char*)ws;
   long long probe = 0, full = 0, fill = 0;
   bool any_rules = false, any_sym_rules = false;
+  int k_max = 0;
   for (int j = 0; j < n_jobs; ++j) {
-    LIDAL_REQUIRE(k[j] > 0 && k[j] < 64 && n_out[j] > 0, "kmap_build_batch: bad map %d (k=%d, rows=%lld)", j, k[j],
+    LIDAL_REQUIRE(k[j] > 0 && k[j] <= 1023 && n_out[j] >= 0, "kmap_build_batch: bad map %d (k=%d, rows=%lld)", j, k[j],
                   (long long)n_out[j]);
+    if (k[j] > k_max) k_max = k[j];
     const TableView t = table_view(tables[j], table_bytes[j]);
     b.tkeys[j] = t.keys; b.tvals[j] = t.vals; b.tmask[j] = t.mask; b.tbits[j] = t.bits; b.tsbits[j] = t.sbits; b.thdr[j] = t.hdr;
     b.coords[j] = (const int4*)out_coords[j]; b.offsets[j] = offsets[j];
     b.nbr[j] = nbr_out[j]; b.nbmaps[j] = (int2*)nbmaps[j]; b.nbsizes[j] = nbsizes[j]; b.koff[j] = (long long*)koff[j];
     b.n_out[j] = n_out[j]; b.k[j] = k[j];
     b.sym[j] = (symmetric[j] && (k[j] & 1) && k[j] >= 3) ? 1 : 0;
-    b.rules[j] = nbmaps[j] != nullptr ? 1 : 0;
+    b.rules[j] = nbsizes[j] != nullptr ? 1 : 0;       // (not nbmaps: an empty map's rule list has no address)
     any_rules |= b.rules[j] != 0;
     any_sym_rules |= b.rules[j] && b.sym[j];
     const int64_t nblocks = cdiv(n_out[j], kTile);
@@ -1030,18 +1043,22 @@ extern "C" int lidal_kmap_build_batch(const void* const* tables, const int64_t* 
     kmap_fill_batch_kernel<<<(unsigned)cdiv(fill, 256), 256, 0, s>>>(b);
     LIDAL_CHECK_LAUNCH("kmap_fill_batch");
   }
-  kmap_probe_batch_kernel<<<(unsigned)probe, kBlock, 0, s>>>(b);
-  LIDAL_CHECK_LAUNCH("kmap_probe_batch");
+  if (probe > 0) {
+    kmap_probe_batch_kernel<<<(unsigned)probe, kBlock, 0, s>>>(b);
+    LIDAL_CHECK_LAUNCH("kmap_probe_batch");
+  }
   if (!any_rules) return 0;
-  if (any_sym_rules) {
+  if (any_sym_rules && full > 0) {
     kmap_count_batch_kernel<<<(unsigned)full, kBlock, 0, s>>>(b);
     LIDAL_CHECK_LAUNCH("kmap_count_batch");
   }
   kmap_scan_batch_kernel<<<(unsigned)n_jobs, 1024, 0, s>>>(b);
   LIDAL_CHECK_LAUNCH("kmap_scan_batch");
-  kmap_compact_batch_kernel<<<(unsigned)full, kBlock, 0, s>>>(b);
-  LIDAL_CHECK_LAUNCH("kmap_compact_batch");
-  kmap_sizes_batch_kernel<<<(unsigned)n_jobs, 64, 0, s>>>(b);
+  if (full > 0) {
+    kmap_compact_batch_kernel<<<(unsigned)full, kBlock, 0, s>>>(b);
+    LIDAL_CHECK_LAUNCH("kmap_compact_batch");
+  }
+  kmap_sizes_batch_kernel<<<(unsigned)n_jobs, (unsigned)align_up(k_max + 1, 64), 0, s>>>(b);
   LIDAL_CHECK_LAUNCH("kmap_sizes_batch");
   return 0;
 }

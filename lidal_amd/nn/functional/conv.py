@@ -206,7 +206,11 @@ class KernelMap:
 
 def build_kernel_map(coords, in_stride, kernel_size, stride, scope=None):
     """Cache-miss branch of upstream conv3d.  Returns (KernelMap, out_coords).  `scope` = the
-    owning SparseTensor's cmaps dict (scopes the level's hash table, query.coords_table)."""
+    owning SparseTensor's cmaps dict (scopes the level's hash table, query.coords_table).
+    Precondition: the rows of `coords` are unique (what voxelisation and spdownsample produce).  The symmetric probe
+    (odd kernel, stride 1) writes each hit's mirror entry nbr[K-1-k][hit] = row, which is one writer per entry only if
+    no two rows share a coordinate; with duplicates the result is not defined.  Any int32 coordinates and batch ids
+    are allowed at stride 1 (offsets are added in wrapping int32); a strided map inherits the ranges of spdownsample."""
     B.require_gpu(coords)
     assert coords.dtype == torch.int
     coords = coords.contiguous()

@@ -10,7 +10,8 @@ __all__ = ['spdownsample', 'unique_sorted', 'downsample_pyramid']
 
 
 def unique_sorted(keys):
-    """Sorted unique of an i64 key vector (== torch.unique(keys) for non-negative keys)."""
+    """Sorted unique of an i64 key vector (== torch.unique(keys)) for keys in 0 <= key < 2^63, which is what sphash
+    makes; raises ValueError for a negative key (the sort is unsigned; found on the device, reported with the count)."""
     B.require_gpu(keys)
     keys = keys.contiguous().view(-1)
     assert keys.dtype == torch.int64
@@ -21,10 +22,17 @@ def unique_sorted(keys):
     ws = B.workspace(ws_bytes, keys.device)
     B.check(B.lib().lidal_unique_sorted_i64(B.ptr(keys), n, B.ptr(out), B.ptr(n_out), B.ptr(ws),
                                             ws_bytes, B.stream()), 'unique_sorted_i64')
-    return out[:int(n_out.item())]
+    m = int(n_out.item())
+    if m < 0:
+        raise ValueError('lidal_amd: unique_sorted needs keys in 0 <= key < 2^63 (sphash output is 60 bit); got a '
+                         'negative key')
+    return out[:m]
 
 
 def spdownsample(coords, stride=2, kernel_size=2, tensor_stride=1):
+    """torchsparse F.spdownsample for 0 <= x, y, z < 65536 and 0 <= batch < 32768 (the packed sort key has 16 bits per
+    coordinate and 15 for the batch index); raises ValueError for a row outside these ranges (found on the device,
+    reported with the row count)."""
     stride = make_ntuple(stride, ndim=3)
     kernel_size = make_ntuple(kernel_size, ndim=3)
     tensor_stride = make_ntuple(tensor_stride, ndim=3)
@@ -42,7 +50,11 @@ def spdownsample(coords, stride=2, kernel_size=2, tensor_stride=1):
     ws = B.workspace(ws_bytes, coords.device)
     B.check(B.lib().lidal_downsample(B.ptr(coords), n, ss[0], ss[1], ss[2], B.ptr(out),
                                      B.ptr(n_out), B.ptr(ws), ws_bytes, B.stream()), 'downsample')
-    return out[:int(n_out.item())]
+    m = int(n_out.item())
+    if m < 0:
+        raise ValueError('lidal_amd: spdownsample needs 0 <= x, y, z < 65536 and 0 <= batch < 32768 (the reference '
+                         'feeds voxel coordinates shifted into [0, full_scale), dataset/sk_dataset.py:156-161)')
+    return out[:m]
 
 
 def downsample_pyramid(coords, levels, tensor_stride=1):
