@@ -41,6 +41,22 @@ __host__ __device__ static inline int64_t align_up(int64_t a, int64_t b) { retur
 
 constexpr int kWave = 64;
 
+// ---- workspace layout: regions of 256-byte granularity taken one after the other from `base` ----
+// A null base makes it a pure size computation, so ONE layout function per builder serves both its
+// lidal_X_workspace_bytes (the total) and its entry point (the pointers): the two cannot drift apart.
+struct Carver {
+  char* base;
+  int64_t off = 0;
+  explicit Carver(void* b) : base((char*)b) {}
+  template <typename T = char>
+  T* take(int64_t count) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off += align_up(count * (int64_t)sizeof(T), 256);
+    return p;
+  }
+  int64_t total() const { return off; }
+};
+
 // ---- FNV-1a-64 folded to 60 bits (torchsparse backend/hash) ----
 __device__ __forceinline__ int64_t fnv60(int32_t x, int32_t y, int32_t z, int32_t b) {
   uint64_t h = 14695981039346656037ULL;

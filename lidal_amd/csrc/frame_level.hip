@@ -327,36 +327,37 @@ __global__ void __launch_bounds__(256) cs_step_kernel(const float* __restrict__ 
   atomicMax(&keys[t], key);
 }
 
-int64_t cs_layout(int64_t n, int num_add, char* base, unsigned long long** keys, int** selected) {
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) { char* q = base ? base + o : nullptr; o += align_up(bytes, 256); return q; };
-  unsigned long long* k = (unsigned long long*)take(8 * (int64_t)std::max(num_add, 1));
-  int* s = (int*)take(4 * std::max<int64_t>(n, 1));
-  if (keys) *keys = k;
-  if (selected) *selected = s;
-  return o;
+// Workspace layouts: one function per builder sizes its scratch (NULL address) and carves it (common.h Carver; the
+// members are the regions in order).
+struct CoresetWs { unsigned long long* keys; int* selected; int64_t total; };
+CoresetWs cs_layout(int64_t n, int num_add, void* ws) {
+  Carver c(ws);
+  return {c.take<unsigned long long>(std::max(num_add, 1)), c.take<int>(std::max<int64_t>(n, 1)), c.total()};
+}
+
+struct UncertaintyWs { float *per_point, *sums; int64_t total; };      // [p, 3] | np_means' partial sums of the columns
+UncertaintyWs uncertainty_layout(int64_t p, void* ws) {
+  Carver c(ws);
+  return {c.take<float>(3 * std::max<int64_t>(p, 1)), c.take<float>(3 * std::max<int64_t>(cdiv(p, NP_BUFSIZE), 1)), c.total()};
 }
 
 }  // namespace
 
 // ---------------------------------------------------------------- ENT / MAR / CONF
-extern "C" int64_t lidal_frame_uncertainty_workspace_bytes(int64_t p) {
-  return align_up(12 * std::max<int64_t>(p, 1), 256) + align_up(12 * std::max<int64_t>(cdiv(p, NP_BUFSIZE), 1), 256);
-}
+extern "C" int64_t lidal_frame_uncertainty_workspace_bytes(int64_t p) { return uncertainty_layout(p, nullptr).total; }
 
 extern "C" int lidal_frame_uncertainty(const float* prob, int64_t p, int c, float* out, void* ws, int64_t ws_bytes,
                                        void* stream) {
   LIDAL_REQUIRE(c >= 2 && c <= FL_MAXC, "frame_uncertainty: classes must be in 2..%d (the margin needs two)", FL_MAXC);
   LIDAL_REQUIRE(p >= 0, "frame_uncertainty: negative point count");
-  LIDAL_REQUIRE(ws_bytes >= lidal_frame_uncertainty_workspace_bytes(p), "frame_uncertainty workspace too small");
+  const UncertaintyWs w = uncertainty_layout(p, ws);
+  LIDAL_REQUIRE(ws_bytes >= w.total, "frame_uncertainty workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  float* per_point = (float*)ws;
-  float* sums = (float*)((char*)ws + align_up(12 * std::max<int64_t>(p, 1), 256));
   if (p > 0) {
-    point_uncertainty_kernel<<<(unsigned)cdiv(p, 256), 256, 0, s>>>(prob, p, c, per_point);
+    point_uncertainty_kernel<<<(unsigned)cdiv(p, 256), 256, 0, s>>>(prob, p, c, w.per_point);
     LIDAL_CHECK_LAUNCH("frame_point_uncertainty");
   }
-  return np_means(per_point, p, 3, sums, out, s);
+  return np_means(w.per_point, p, 3, w.sums, out, s);
 }
 
 // ---------------------------------------------------------------- SEGENT
@@ -397,7 +398,7 @@ extern "C" int lidal_frame_feature(const float* feat, int64_t p, int d, float* o
 
 // ---------------------------------------------------------------- CSET greedy k-center
 extern "C" int64_t lidal_coreset_workspace_bytes(int64_t n, int num_add) {
-  return cs_layout(n, num_add, nullptr, nullptr, nullptr);
+  return cs_layout(n, num_add, nullptr).total;
 }
 
 extern "C" int lidal_coreset(const float* feats, int64_t n, int d, const int64_t* labeled, int64_t n_labeled, int num_add,
@@ -409,11 +410,11 @@ extern "C" int lidal_coreset(const float* feats, int64_t n, int d, const int64_t
   LIDAL_REQUIRE(n_labeled <= (int64_t)CS_LCHUNK * 65535, "coreset: at most %d labeled frames", CS_LCHUNK * 65535);
   LIDAL_REQUIRE(num_add >= 0 && (int64_t)num_add <= n - n_labeled,
                 "coreset: num_add (%d) must be in 0..the unlabeled count (%lld)", num_add, (long long)(n - n_labeled));
-  LIDAL_REQUIRE(ws_bytes >= lidal_coreset_workspace_bytes(n, num_add), "coreset workspace too small");
+  const CoresetWs w = cs_layout(n, num_add, ws);
+  LIDAL_REQUIRE(ws_bytes >= w.total, "coreset workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  unsigned long long* keys;
-  int* selected;
-  cs_layout(n, num_add, (char*)ws, &keys, &selected);
+  unsigned long long* keys = w.keys;
+  int* selected = w.selected;
   const unsigned gn = (unsigned)cdiv(n, 256);
   LIDAL_HIP(hipMemsetAsync(status_dev, 0, 8, s));
   LIDAL_HIP(hipMemsetAsync(keys, 0, 8 * (size_t)std::max(num_add, 1), s));

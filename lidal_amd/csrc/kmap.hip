@@ -120,40 +120,30 @@ __global__ void __launch_bounds__(kBlock) head_compact_kernel(const uint64_t* __
     *n_out = ((bad != nullptr && *bad) || (signed_keys && (s[n - 1] >> 63))) ? -1 : offsets[nblocks];
 }
 
+// Workspace layouts.  Each builder below has ONE layout function: given the scratch address it returns a struct of
+// typed pointers and the total, given NULL it only sizes (common.h Carver).  lidal_X_workspace_bytes returns that total
+// and the entry point uses those pointers; no offset is computed anywhere else.  The members of a struct are its
+// regions IN ORDER (a braced initialiser list is evaluated left to right); a zero count sizes as one; `spare` regions
+// hold nothing and are kept so that the sizes callers see stay what they were.
 struct UniqueWs {
-  uint64_t* sorted;
-  int* counts;
-  int64_t* offsets;
-  void* sort_tmp;
-  size_t sort_tmp_bytes;
-  int64_t total;
+  uint64_t* sorted; int* counts; int64_t* offsets; char* sort_tmp;
+  int* flag;                 // a caller's "input refused" flag (lidal_downsample: `bad`)
+  int64_t sort_tmp_bytes, total;
 };
-
-UniqueWs carve_unique_ws(void* ws, int64_t n) {
-  UniqueWs u;
-  int64_t nblocks = cdiv(n > 0 ? n : 1, kTile);
-  const size_t tmp = (size_t)radix_sort_ws_bytes(n > 0 ? n : 1, 8, false);
-  char* p = (char*)ws;
-  int64_t o = 0;
-  u.sorted = (uint64_t*)(p + o); o += align_up(8 * (n > 0 ? n : 1), 256);
-  u.counts = (int*)(p + o);      o += align_up(4 * nblocks, 256);
-  u.offsets = (int64_t*)(p + o); o += align_up(8 * (nblocks + 1), 256);
-  u.sort_tmp = (void*)(p + o);   o += align_up((int64_t)tmp, 256);
-  u.sort_tmp_bytes = tmp;
-  u.total = o;
-  return u;
+UniqueWs unique_layout(int64_t n, void* ws) {
+  const int64_t q = n > 0 ? n : 1, nblocks = cdiv(q, kTile), tmp = radix_sort_ws_bytes(q, 8, false);
+  Carver c(ws);
+  return {c.take<uint64_t>(q), c.take<int>(nblocks), c.take<int64_t>(nblocks + 1), c.take(tmp), c.take<int>(1), tmp, c.total()};
 }
 
-int unique_sorted_u64(const uint64_t* keys, int64_t n, int64_t* out, int64_t* n_out_dev, void* ws,
-                      int64_t ws_bytes, int end_bit, hipStream_t s, const int* bad = nullptr, int signed_keys = 0) {
+// (the caller has checked that its scratch holds u.total bytes)
+int unique_sorted_u64(const uint64_t* keys, int64_t n, int64_t* out, int64_t* n_out_dev, const UniqueWs& u,
+                      int end_bit, hipStream_t s, const int* bad = nullptr, int signed_keys = 0) {
   if (n == 0) {
     LIDAL_HIP(hipMemsetAsync(n_out_dev, 0, 8, s));
     return 0;
   }
-  UniqueWs u = carve_unique_ws(ws, n);
-  LIDAL_REQUIRE(ws_bytes >= u.total, "unique workspace too small: %lld < %lld",
-                (long long)ws_bytes, (long long)u.total);
-  if (int rc = radix_sort(keys, nullptr, u.sorted, nullptr, n, 8, end_bit, u.sort_tmp, (int64_t)u.sort_tmp_bytes, s))
+  if (int rc = radix_sort(keys, nullptr, u.sorted, nullptr, n, 8, end_bit, u.sort_tmp, u.sort_tmp_bytes, s))
     return rc;
   int64_t nblocks = cdiv(n, kTile);
   head_count_kernel<<<(int)nblocks, kBlock, 0, s>>>(u.sorted, n, u.counts);
@@ -668,19 +658,71 @@ __global__ void __launch_bounds__(kBlock) rows_compact_kernel(const uint64_t* __
   if (blockIdx.x == 0 && threadIdx.x == 0) *n_out = offsets[nblocks];
 }
 
-size_t voxel_sort_tmp_bytes(int64_t n) { return (size_t)radix_sort_ws_bytes(n > 0 ? n : 1, 8, true); }
+struct DownsampleWs { uint64_t* packed; int64_t* uniq; UniqueWs unique; int64_t total; };      // unique.flag is `bad`
+DownsampleWs downsample_layout(int64_t n, void* ws) {
+  const int64_t q = n > 0 ? n : 1;
+  Carver c(ws);
+  return {c.take<uint64_t>(q), c.take<int64_t>(q), unique_layout(n, c.take(unique_layout(n, nullptr).total)), c.total()};
+}
+
+struct PyramidWs { uint64_t *keys, *sorted; int* counts; int64_t* offs; char* sort_tmp; int* bad; int64_t sort_tmp_bytes, total; };
+PyramidWs pyramid_layout(int64_t n, int levels, void* ws) {
+  const int64_t q = (n > 0 ? n : 1) * (levels > 0 ? levels : 1), nblocks = cdiv(q, kTile), tmp = radix_sort_ws_bytes(q, 8, false);
+  Carver c(ws);
+  return {c.take<uint64_t>(q), c.take<uint64_t>(q), c.take<int>(nblocks), c.take<int64_t>(nblocks + 1), c.take(tmp),
+          c.take<int>(1), tmp, c.total()};
+}
+
+// per-(offset, block) hit counts and their scan
+struct KmapWs { int* counts; int64_t* offs; char* spare; int64_t total; };
+KmapWs kmap_layout(int64_t n_out, int k, void* ws) {
+  const int64_t nblocks = cdiv(n_out > 0 ? n_out : 1, kTile);
+  Carver c(ws);
+  return {c.take<int>(nblocks * k), c.take<int64_t>(nblocks * k + 1), c.take(256), c.total()};
+}
+// lidal_kmap_build_batch: the single-map layout of every job, one after the other, and a spare region (jobs may be NULL)
+int64_t kmap_batch_layout(const int64_t* n_out, const int32_t* k, int n_jobs, void* ws, KmapWs* jobs) {
+  Carver c(ws);
+  for (int j = 0; j < n_jobs; ++j) {
+    const KmapWs w = kmap_layout(n_out[j], k[j], c.take(kmap_layout(n_out[j], k[j], nullptr).total));
+    if (jobs != nullptr) jobs[j] = w;
+  }
+  c.take(256);
+  return c.total();
+}
+
+// lidal_kmap_order and lidal_kmap_order_batch (q = all rows of the call; `svals` is the batch form's alone: the
+// single form sorts the row ids straight into the caller's perm)
+struct OrderWs { unsigned *keys, *skeys; int *vals, *svals; char *sort_tmp, *spare; int64_t sort_tmp_bytes, total; };
+OrderWs order_layout(int64_t n_rows, void* ws) {
+  const int64_t q = n_rows > 0 ? n_rows : 1, tmp = sort_pairs_ws_bytes(q);
+  Carver c(ws);
+  return {c.take<unsigned>(q), c.take<unsigned>(q), c.take<int>(q), c.take<int>(q), c.take(tmp), c.take(256), tmp, c.total()};
+}
+
+// scaled f64 [p, 3] | min / max partials f64 [blocks, 6] | offset f64 [3] | keys, sorted keys | ids, sorted ids | scan
+struct VoxelizeWs {
+  double *scaled, *part, *offset; uint64_t *keys, *skeys; int *ids, *sids, *counts; int64_t* offs; char *sort_tmp, *spare;
+  int64_t sort_tmp_bytes, total;
+};
+VoxelizeWs voxelize_layout(int64_t p, void* ws) {
+  const int64_t q = p > 0 ? p : 1, blocks = cdiv(q, 256), nb = cdiv(q, kTile), tmp = radix_sort_ws_bytes(q, 8, true);
+  Carver c(ws);
+  return {c.take<double>(3 * q), c.take<double>(6 * blocks), c.take<double>(3), c.take<uint64_t>(q), c.take<uint64_t>(q),
+          c.take<int>(q), c.take<int>(q), c.take<int>(nb), c.take<int64_t>(nb + 1), c.take(tmp), c.take(256), tmp, c.total()};
+}
 
 }  // namespace
 
-extern "C" int64_t lidal_unique_workspace_bytes(int64_t n) {
-  return carve_unique_ws(nullptr, n).total + 256;
-}
+extern "C" int64_t lidal_unique_workspace_bytes(int64_t n) { return unique_layout(n, nullptr).total; }
 
 extern "C" int lidal_unique_sorted_i64(const int64_t* keys, int64_t n, int64_t* out,
                                        int64_t* n_out_dev, void* ws, int64_t ws_bytes,
                                        void* stream) {
-  return unique_sorted_u64((const uint64_t*)keys, n, out, n_out_dev, ws, ws_bytes, 64,
-                           (hipStream_t)stream, nullptr, 1);
+  const UniqueWs u = unique_layout(n, ws);
+  LIDAL_REQUIRE(n == 0 || ws_bytes >= u.total, "unique workspace too small: %lld < %lld", (long long)ws_bytes,
+                (long long)u.total);
+  return unique_sorted_u64((const uint64_t*)keys, n, out, n_out_dev, u, 64, (hipStream_t)stream, nullptr, 1);
 }
 
 extern "C" int lidal_downsample(const int32_t* coords, int64_t n, int sx, int sy, int sz,
@@ -692,21 +734,16 @@ extern "C" int lidal_downsample(const int32_t* coords, int64_t n, int sx, int sy
     LIDAL_HIP(hipMemsetAsync(n_out_dev, 0, 8, s));
     return 0;
   }
-  // workspace: [packed keys 8n][unique keys 8n][unique ws]
-  int64_t kb = align_up(8 * n, 256);
-  int64_t need = 2 * kb + lidal_unique_workspace_bytes(n);
-  LIDAL_REQUIRE(ws_bytes >= need, "downsample workspace too small: %lld < %lld",
-                (long long)ws_bytes, (long long)need);
-  uint64_t* packed = (uint64_t*)ws;
-  int64_t* uniq = (int64_t*)((char*)ws + kb);
-  void* uws = (char*)ws + 2 * kb;
-  int* bad = (int*)((char*)ws + need - 256);                 // (the slack at the end of the unique workspace)
+  const DownsampleWs w = downsample_layout(n, ws);
+  LIDAL_REQUIRE(ws_bytes >= w.total, "downsample workspace too small: %lld < %lld",
+                (long long)ws_bytes, (long long)w.total);
+  int* bad = w.unique.flag;
   LIDAL_HIP(hipMemsetAsync(bad, 0, 4, s));
-  pack_coords_kernel<<<(int)cdiv(n, 256), 256, 0, s>>>((const int4*)coords, n, sx, sy, sz, packed, bad);
+  pack_coords_kernel<<<(int)cdiv(n, 256), 256, 0, s>>>((const int4*)coords, n, sx, sy, sz, w.packed, bad);
   LIDAL_CHECK_LAUNCH("pack_coords");
-  int rc = unique_sorted_u64(packed, n, uniq, n_out_dev, uws, ws_bytes - 2 * kb, 63, s, bad);
+  int rc = unique_sorted_u64(w.packed, n, w.uniq, n_out_dev, w.unique, 63, s, bad);
   if (rc) return rc;
-  unpack_coords_kernel<<<(int)cdiv(n, 256), 256, 0, s>>>(uniq, n_out_dev, (int4*)out);
+  unpack_coords_kernel<<<(int)cdiv(n, 256), 256, 0, s>>>(w.uniq, n_out_dev, (int4*)out);
   LIDAL_CHECK_LAUNCH("unpack_coords");
   return 0;
 }
@@ -768,10 +805,7 @@ __global__ void __launch_bounds__(kBlock) pyramid_compact_kernel(const uint64_t*
 }  // namespace
 
 extern "C" int64_t lidal_downsample_pyramid_workspace_bytes(int64_t n, int levels) {
-  const int64_t q = (n > 0 ? n : 1) * (levels > 0 ? levels : 1);
-  const int64_t nblocks = cdiv(q, kTile);
-  return 2 * align_up(8 * q, 256) + align_up(4 * nblocks, 256) + align_up(8 * (nblocks + 1), 256) +
-         align_up(radix_sort_ws_bytes(q, 8, false), 256) + 256;
+  return pyramid_layout(n, levels, nullptr).total;
 }
 
 // coords i32 [n, 4] at tensor stride (sx, sy, sz); out i32 [levels * n, 4] capacity: level l (1-based: stride
@@ -786,37 +820,26 @@ extern "C" int lidal_downsample_pyramid(const int32_t* coords, int64_t n, int sx
     LIDAL_HIP(hipMemsetAsync(starts_dev, 0, 8 * (levels + 1), s));
     return 0;
   }
-  LIDAL_REQUIRE(ws_bytes >= lidal_downsample_pyramid_workspace_bytes(n, levels), "downsample_pyramid ws too small");
+  const PyramidWs w = pyramid_layout(n, levels, ws);
+  LIDAL_REQUIRE(ws_bytes >= w.total, "downsample_pyramid ws too small");
   const int64_t q = n * levels, nblocks = cdiv(q, kTile);
-  char* w = (char*)ws;
-  uint64_t* keys = (uint64_t*)w;    w += align_up(8 * q, 256);
-  uint64_t* sorted = (uint64_t*)w;  w += align_up(8 * q, 256);
-  int* counts = (int*)w;            w += align_up(4 * nblocks, 256);
-  int64_t* offs = (int64_t*)w;      w += align_up(8 * (nblocks + 1), 256);
-  void* tmp = (void*)w;
-  int* bad = (int*)((char*)ws + lidal_downsample_pyramid_workspace_bytes(n, levels) - 256);      // (the slack at the end)
-  LIDAL_HIP(hipMemsetAsync(bad, 0, 4, s));
-  pyramid_keys_kernel<<<(unsigned)cdiv(n, 256), 256, 0, s>>>((const int4*)coords, n, levels, sx, sy, sz, keys, bad);
+  LIDAL_HIP(hipMemsetAsync(w.bad, 0, 4, s));
+  pyramid_keys_kernel<<<(unsigned)cdiv(n, 256), 256, 0, s>>>((const int4*)coords, n, levels, sx, sy, sz, w.keys, w.bad);
   LIDAL_CHECK_LAUNCH("pyramid_keys");
-  if (int rc = radix_sort(keys, nullptr, sorted, nullptr, q, 8, 63, tmp, radix_sort_ws_bytes(q, 8, false), s)) return rc;
-  head_count_kernel<<<(unsigned)nblocks, kBlock, 0, s>>>(sorted, q, counts);
+  if (int rc = radix_sort(w.keys, nullptr, w.sorted, nullptr, q, 8, 63, w.sort_tmp, w.sort_tmp_bytes, s)) return rc;
+  head_count_kernel<<<(unsigned)nblocks, kBlock, 0, s>>>(w.sorted, q, w.counts);
   LIDAL_CHECK_LAUNCH("head_count");
-  scan_counts_kernel<<<1, 1024, 0, s>>>(counts, nblocks, offs);
+  scan_counts_kernel<<<1, 1024, 0, s>>>(w.counts, nblocks, w.offs);
   LIDAL_CHECK_LAUNCH("scan_counts");
-  pyramid_compact_kernel<<<(unsigned)nblocks, kBlock, 0, s>>>(sorted, q, n, levels, offs, nblocks, (int4*)out,
-                                                              starts_dev, bad);
+  pyramid_compact_kernel<<<(unsigned)nblocks, kBlock, 0, s>>>(w.sorted, q, n, levels, w.offs, nblocks, (int4*)out,
+                                                              starts_dev, w.bad);
   LIDAL_CHECK_LAUNCH("pyramid_compact");
   return 0;
 }
 
-extern "C" int64_t lidal_downsample_workspace_bytes(int64_t n) {
-  return 2 * align_up(8 * (n > 0 ? n : 1), 256) + lidal_unique_workspace_bytes(n);
-}
+extern "C" int64_t lidal_downsample_workspace_bytes(int64_t n) { return downsample_layout(n, nullptr).total; }
 
-extern "C" int64_t lidal_kmap_workspace_bytes(int64_t n_out, int k) {
-  int64_t nblocks = cdiv(n_out > 0 ? n_out : 1, kTile);
-  return align_up(4 * nblocks * k, 256) + align_up(8 * (nblocks * k + 1), 256) + 256;
-}
+extern "C" int64_t lidal_kmap_workspace_bytes(int64_t n_out, int k) { return kmap_layout(n_out, k, nullptr).total; }
 
 extern "C" int lidal_kmap_build(const void* table, int64_t table_bytes, const int32_t* out_coords,
                                 int64_t n_out, const int32_t* offsets, int k, int symmetric,
@@ -833,10 +856,11 @@ extern "C" int lidal_kmap_build(const void* table, int64_t table_bytes, const in
     }
     return 0;
   }
-  LIDAL_REQUIRE(ws_bytes >= lidal_kmap_workspace_bytes(n_out, k), "kmap workspace too small");
+  const KmapWs w = kmap_layout(n_out, k, ws);
+  LIDAL_REQUIRE(ws_bytes >= w.total, "kmap workspace too small");
   int64_t nblocks = cdiv(n_out, kTile);
-  int* counts = (int*)ws;
-  int64_t* offs = (int64_t*)((char*)ws + align_up(4 * nblocks * k, 256));
+  int* counts = w.counts;
+  int64_t* offs = w.offs;
   bool counted = false;
   if (want_table) {
     TableView t = table_view(table, table_bytes);
@@ -991,9 +1015,7 @@ __global__ void __launch_bounds__(1024) kmap_sizes_batch_kernel(KmapBatch b) {
 }  // namespace
 
 extern "C" int64_t lidal_kmap_build_batch_workspace_bytes(const int64_t* n_out, const int32_t* k, int n_jobs) {
-  int64_t total = 256;
-  for (int j = 0; j < n_jobs; ++j) total += lidal_kmap_workspace_bytes(n_out[j], k[j]);
-  return total;
+  return kmap_batch_layout(n_out, k, n_jobs, nullptr, nullptr);
 }
 
 // Host arrays of length n_jobs (<= 12): the arguments of lidal_kmap_build per map.  nbsizes[j] == NULL: table only.
@@ -1007,11 +1029,11 @@ extern "C" int lidal_kmap_build_batch(const void* const* tables, const int64_t* 
   hipStream_t s = (hipStream_t)stream;
   LIDAL_REQUIRE(n_jobs >= 0 && n_jobs <= MAX_KMAP_JOBS, "kmap_build_batch: at most %d maps", MAX_KMAP_JOBS);
   if (n_jobs == 0) return 0;
-  LIDAL_REQUIRE(ws_bytes >= lidal_kmap_build_batch_workspace_bytes(n_out, k, n_jobs), "kmap_build_batch ws too small");
+  KmapWs job_ws[MAX_KMAP_JOBS];
+  LIDAL_REQUIRE(ws_bytes >= kmap_batch_layout(n_out, k, n_jobs, ws, job_ws), "kmap_build_batch ws too small");
   KmapBatch b;
   memset(&b, 0, sizeof(b));
   b.n_jobs = n_jobs;
-  char* w = (char*)ws;
   long long probe = 0, full = 0, fill = 0;
   bool any_rules = false, any_sym_rules = false;
   int k_max = 0;
@@ -1030,9 +1052,8 @@ extern "C" int lidal_kmap_build_batch(const void* const* tables, const int64_t* 
     any_sym_rules |= b.rules[j] && b.sym[j];
     const int64_t nblocks = cdiv(n_out[j], kTile);
     b.nblocks[j] = nblocks;
-    b.counts[j] = (int*)w;
-    b.offs[j] = (long long*)(w + align_up(4 * nblocks * k[j], 256));
-    w += lidal_kmap_workspace_bytes(n_out[j], k[j]);
+    b.counts[j] = job_ws[j].counts;
+    b.offs[j] = (long long*)job_ws[j].offs;
     b.probe0[j] = probe; b.full0[j] = full; b.fill0[j] = fill;
     probe += nblocks * (b.sym[j] ? k[j] / 2 : k[j]);
     full += nblocks * k[j];
@@ -1074,12 +1095,7 @@ extern "C" int lidal_kmap_invert(const int32_t* nbr_out, int64_t n_out, int k, i
   return 0;
 }
 
-static int64_t order_sort_tmp_bytes(int64_t q) { return sort_pairs_ws_bytes(q); }
-
-extern "C" int64_t lidal_kmap_order_workspace_bytes(int64_t n_rows) {
-  int64_t q = n_rows > 0 ? n_rows : 1;
-  return 4 * align_up(4 * q, 256) + align_up(order_sort_tmp_bytes(q), 256) + 256;
-}
+extern "C" int64_t lidal_kmap_order_workspace_bytes(int64_t n_rows) { return order_layout(n_rows, nullptr).total; }
 
 extern "C" int lidal_kmap_order(const int32_t* nbr, int64_t n_rows, int k, int32_t* perm,
                                 int32_t* nbr_perm, uint32_t* tile_masks, void* ws,
@@ -1087,16 +1103,14 @@ extern "C" int lidal_kmap_order(const int32_t* nbr, int64_t n_rows, int k, int32
   hipStream_t s = (hipStream_t)stream;
   LIDAL_REQUIRE(k > 0 && k <= 32, "kmap_order: kernel volume %d must be <= 32", k);
   if (n_rows == 0) return 0;
-  LIDAL_REQUIRE(ws_bytes >= lidal_kmap_order_workspace_bytes(n_rows), "kmap_order ws too small");
-  int64_t q = n_rows, a = align_up(4 * q, 256);
-  unsigned* keys = (unsigned*)ws;
-  unsigned* skeys = (unsigned*)((char*)ws + a);
-  int* vals = (int*)((char*)ws + 2 * a);
-  void* tmp = (char*)ws + 3 * a;
+  const OrderWs w = order_layout(n_rows, ws);
+  LIDAL_REQUIRE(ws_bytes >= w.total, "kmap_order ws too small");
+  const int64_t q = n_rows;
+  unsigned* skeys = w.skeys;
   const BitRank rank = bit_rank(k);
-  row_mask_kernel<<<(unsigned)cdiv(q, 256), 256, 0, s>>>(nbr, q, k, rank, keys, vals);
+  row_mask_kernel<<<(unsigned)cdiv(q, 256), 256, 0, s>>>(nbr, q, k, rank, w.keys, w.vals);
   LIDAL_CHECK_LAUNCH("row_mask");
-  if (int rc = sort_pairs_u32(keys, vals, skeys, perm, q, k, tmp, order_sort_tmp_bytes(q), s)) return rc;
+  if (int rc = sort_pairs_u32(w.keys, w.vals, skeys, perm, q, k, w.sort_tmp, w.sort_tmp_bytes, s)) return rc;
   permute_table_kernel<<<dim3((unsigned)cdiv(q, 256), (unsigned)k), 256, 0, s>>>(nbr, q, perm,
                                                                                  nbr_perm);
   LIDAL_CHECK_LAUNCH("permute_table");
@@ -1208,38 +1222,23 @@ extern "C" int lidal_kmap_order_batch(const int32_t* const* nbr, const int64_t* 
   }
   for (int j = n_jobs; j <= MAX_ORDER_JOBS; ++j) { b.row0[j] = rows; b.tile0[j] = tiles; }
   if (rows == 0) return 0;
-  LIDAL_REQUIRE(ws_bytes >= lidal_kmap_order_workspace_bytes(rows), "kmap_order_batch ws too small");
-  const int64_t a = align_up(4 * rows, 256);
-  unsigned* keys = (unsigned*)ws;
-  unsigned* skeys = (unsigned*)((char*)ws + a);
-  int* vals = (int*)((char*)ws + 2 * a);
-  // the sorted row ids land in the first table's perm-sized scratch? no: perm arrays are per table, so
-  // the sorted ids go to a scratch slice and permute_table_batch distributes them
-  int* svals = (int*)((char*)ws + 3 * a);
-  void* tmp = (char*)ws + 4 * a;
+  const OrderWs w = order_layout(rows, ws);
+  LIDAL_REQUIRE(ws_bytes >= w.total, "kmap_order_batch ws too small");
+  // (the perm arrays are per table, so the sorted row ids go to scratch and permute_table_batch distributes them)
   const BitRank rank = bit_rank(k);
-  row_mask_batch_kernel<<<(unsigned)cdiv(rows, 256), 256, 0, s>>>(b, rank, keys, vals);
+  row_mask_batch_kernel<<<(unsigned)cdiv(rows, 256), 256, 0, s>>>(b, rank, w.keys, w.vals);
   LIDAL_CHECK_LAUNCH("row_mask_batch");
-  if (int rc = sort_pairs_u32(keys, vals, skeys, svals, rows, k + jbits, tmp, order_sort_tmp_bytes(rows), s)) return rc;
-  permute_table_batch_kernel<<<dim3((unsigned)cdiv(rows, 256), (unsigned)k), 256, 0, s>>>(b, svals);
+  if (int rc = sort_pairs_u32(w.keys, w.vals, w.skeys, w.svals, rows, k + jbits, w.sort_tmp, w.sort_tmp_bytes, s))
+    return rc;
+  permute_table_batch_kernel<<<dim3((unsigned)cdiv(rows, 256), (unsigned)k), 256, 0, s>>>(b, w.svals);
   LIDAL_CHECK_LAUNCH("permute_table_batch");
-  tile_or_batch_kernel<<<(unsigned)cdiv(tiles, 4), 256, 0, s>>>(b, rank, skeys);
+  tile_or_batch_kernel<<<(unsigned)cdiv(tiles, 4), 256, 0, s>>>(b, rank, w.skeys);
   LIDAL_CHECK_LAUNCH("tile_or_batch");
   return 0;
 }
 
 // ---- input voxelisation -------------------------------------------------------------------------
-extern "C" int64_t lidal_voxelize_points_workspace_bytes(int64_t p) {
-  int64_t q = p > 0 ? p : 1;
-  int64_t blocks = cdiv(q, 256), nb = cdiv(q, kTile);
-  return align_up(24 * q, 256)              /* scaled f64 [p,3] */
-         + align_up(48 * blocks, 256)       /* min/max partials */
-         + 256                              /* offset[3], n_invalid */
-         + 2 * align_up(8 * q, 256)         /* keys, sorted keys */
-         + 2 * align_up(4 * q, 256)         /* ids, sorted ids */
-         + align_up(4 * nb, 256) + align_up(8 * (nb + 1), 256)
-         + align_up((int64_t)voxel_sort_tmp_bytes(q), 256) + 256;
-}
+extern "C" int64_t lidal_voxelize_points_workspace_bytes(int64_t p) { return voxelize_layout(p, nullptr).total; }
 
 extern "C" int lidal_voxelize_points(const float* points, const float* intensity, int64_t p,
                                      const double* m_dev, const double* rnd_dev, double scale,
@@ -1254,31 +1253,21 @@ extern "C" int lidal_voxelize_points(const float* points, const float* intensity
     LIDAL_HIP(hipMemsetAsync(n_out_dev, 0, 8, s));
     return 0;
   }
-  LIDAL_REQUIRE(ws_bytes >= lidal_voxelize_points_workspace_bytes(p), "voxelize_points ws too small");
+  const VoxelizeWs w = voxelize_layout(p, ws);
+  LIDAL_REQUIRE(ws_bytes >= w.total, "voxelize_points ws too small");
   int64_t blocks = cdiv(p, 256), nb = cdiv(p, kTile);
-  char* w = (char*)ws;
-  double* scaled = (double*)w;      w += align_up(24 * p, 256);
-  double* part = (double*)w;        w += align_up(48 * blocks, 256);
-  double* offset = (double*)w;      w += 256;
-  uint64_t* keys = (uint64_t*)w;    w += align_up(8 * p, 256);
-  uint64_t* skeys = (uint64_t*)w;   w += align_up(8 * p, 256);
-  int* ids = (int*)w;               w += align_up(4 * p, 256);
-  int* sids = (int*)w;              w += align_up(4 * p, 256);
-  int* counts = (int*)w;            w += align_up(4 * nb, 256);
-  int64_t* offs = (int64_t*)w;      w += align_up(8 * (nb + 1), 256);
-  void* tmp = (void*)w;
-  affine_kernel<<<(unsigned)blocks, 256, 0, s>>>(points, intensity, p, m_dev, scale, feats_p, scaled, part);
+  affine_kernel<<<(unsigned)blocks, 256, 0, s>>>(points, intensity, p, m_dev, scale, feats_p, w.scaled, w.part);
   LIDAL_CHECK_LAUNCH("affine");
-  voxel_offset_kernel<<<1, 256, 0, s>>>(part, blocks, rnd_dev, (double)full_scale, offset);
+  voxel_offset_kernel<<<1, 256, 0, s>>>(w.part, blocks, rnd_dev, (double)full_scale, w.offset);
   LIDAL_CHECK_LAUNCH("voxel_offset");
-  voxel_keys_kernel<<<(unsigned)blocks, 256, 0, s>>>(scaled, p, offset, full_scale, keys, ids, n_invalid_dev);
+  voxel_keys_kernel<<<(unsigned)blocks, 256, 0, s>>>(w.scaled, p, w.offset, full_scale, w.keys, w.ids, n_invalid_dev);
   LIDAL_CHECK_LAUNCH("voxel_keys");
-  if (int rc = radix_sort(keys, ids, skeys, sids, p, 8, 39, tmp, (int64_t)voxel_sort_tmp_bytes(p), s)) return rc;
-  head_count_kernel<<<(unsigned)nb, kBlock, 0, s>>>(skeys, p, counts);
+  if (int rc = radix_sort(w.keys, w.ids, w.skeys, w.sids, p, 8, 39, w.sort_tmp, w.sort_tmp_bytes, s)) return rc;
+  head_count_kernel<<<(unsigned)nb, kBlock, 0, s>>>(w.skeys, p, w.counts);
   LIDAL_CHECK_LAUNCH("head_count");
-  scan_counts_kernel<<<1, 1024, 0, s>>>(counts, nb, offs);
+  scan_counts_kernel<<<1, 1024, 0, s>>>(w.counts, nb, w.offs);
   LIDAL_CHECK_LAUNCH("scan_counts");
-  rows_compact_kernel<<<(unsigned)nb, kBlock, 0, s>>>(skeys, sids, p, offs, nb, coords_v, unique_idx,
+  rows_compact_kernel<<<(unsigned)nb, kBlock, 0, s>>>(w.skeys, w.sids, p, w.offs, nb, coords_v, unique_idx,
                                                       inverse, n_out_dev);
   LIDAL_CHECK_LAUNCH("rows_compact");
   return 0;

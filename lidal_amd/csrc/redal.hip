@@ -455,44 +455,30 @@ __global__ void km_starts_kernel(const int* __restrict__ counts, int k, int* __r
   for (int j = 0; j < k; ++j) { starts[j] = s; s += counts[j]; }
 }
 
+// Workspace layouts: one function per builder sizes its scratch (NULL address) and carves it (common.h Carver; the
+// members are the regions in order).
 struct KmWs {
   double *closest, *D, *cs, *tot, *off, *pot_t, *pot, *mind2, *cnew, *shift;
   int *cand, *best, *old, *keys, *iota, *skeys, *order, *counts, *starts, *changed;
-  void* sort_tmp;
-  int64_t sort_bytes;
+  char* sort_tmp;
+  int64_t sort_bytes, total;
 };
+KmWs km_layout(int64_t n_rows, int d, int k, int trials, void* ws) {
+  const int64_t n = n_rows > 0 ? n_rows : 1, nc = cdiv(n, KM_CHUNK), tr = trials > 0 ? trials : 1;
+  const int64_t tmp = radix_sort_ws_bytes(n, 4, true);
+  Carver c(ws);
+  return {c.take<double>(n), c.take<double>(n * tr), c.take<double>(n), c.take<double>(nc * tr), c.take<double>(nc * tr),
+          c.take<double>(tr), c.take<double>(1), c.take<double>(n), c.take<double>((int64_t)k * d), c.take<double>(1),
+          c.take<int>(tr), c.take<int>(1), c.take<int>(n), c.take<int>(n), c.take<int>(n), c.take<int>(n), c.take<int>(n),
+          c.take<int>(k), c.take<int>(k), c.take<int>(1), c.take(tmp), tmp, c.total()};
+}
 
-int64_t km_layout(int64_t n, int d, int k, int trials, char* base, KmWs* w) {
-  const int64_t nc = cdiv(n, KM_CHUNK);
-  const int64_t tr = trials > 0 ? trials : 1;
-  const int64_t sort_bytes = radix_sort_ws_bytes(n, 4, true);
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) { char* p = base ? base + o : nullptr; o += align_up(bytes, 256); return p; };
-  KmWs v;
-  v.closest = (double*)take(8 * n);
-  v.D = (double*)take(8 * n * tr);
-  v.cs = (double*)take(8 * n);
-  v.tot = (double*)take(8 * nc * tr);
-  v.off = (double*)take(8 * nc * tr);
-  v.pot_t = (double*)take(8 * tr);
-  v.pot = (double*)take(8);
-  v.mind2 = (double*)take(8 * n);
-  v.cnew = (double*)take(8 * (int64_t)k * d);
-  v.shift = (double*)take(8);
-  v.cand = (int*)take(4 * tr);
-  v.best = (int*)take(4);
-  v.old = (int*)take(4 * n);
-  v.keys = (int*)take(4 * n);
-  v.iota = (int*)take(4 * n);
-  v.skeys = (int*)take(4 * n);
-  v.order = (int*)take(4 * n);
-  v.counts = (int*)take(4 * (int64_t)k);
-  v.starts = (int*)take(4 * (int64_t)k);
-  v.changed = (int*)take(4);
-  v.sort_tmp = take(sort_bytes);
-  v.sort_bytes = sort_bytes;
-  if (w) *w = v;
-  return o;
+// k-NN: the points as f64, the cell bounds of the scan, the search grid and the scratch of its build
+struct KnnWs { double* pts; int* bounds; char *grid, *grid_ws; int64_t grid_bytes, grid_ws_bytes, total; };
+KnnWs knn_layout(int64_t p, void* ws) {
+  const int64_t q = p > 0 ? p : 1, gb = lidal_nn_grid_bytes(q), gwb = lidal_nn_grid_workspace_bytes(q);
+  Carver c(ws);
+  return {c.take<double>(3 * q), c.take<int>(6), c.take(gb), c.take(gwb), gb, gwb, c.total()};
 }
 
 // one assignment + its counts; rows of empty clusters relocated (host side: rare)
@@ -547,10 +533,7 @@ int km_total(const double* v, int64_t n, const KmWs& w, hipStream_t s, double* o
 }  // namespace
 
 // ---------------------------------------------------------------- k-NN / surface variation
-extern "C" int64_t lidal_knn_workspace_bytes(int64_t p) {
-  const int64_t q = p > 0 ? p : 1;
-  return align_up(24 * q, 256) + 256 + align_up(lidal_nn_grid_bytes(q), 256) + align_up(lidal_nn_grid_workspace_bytes(q), 256);
-}
+extern "C" int64_t lidal_knn_workspace_bytes(int64_t p) { return knn_layout(p, nullptr).total; }
 
 static int knn_run(const float* xyz, int64_t p, int k, double cell, int32_t* knn, float* sigma, float threshold, void* ws,
                    int64_t ws_bytes, void* stream) {
@@ -559,19 +542,17 @@ static int knn_run(const float* xyz, int64_t p, int k, double cell, int32_t* knn
                 (long long)p, k);
   LIDAL_REQUIRE(p < 0x7FFFFFFF, "knn: at most 2^31 - 1 points");
   LIDAL_REQUIRE(cell > 0, "knn: cell must be positive");
-  LIDAL_REQUIRE(ws_bytes >= lidal_knn_workspace_bytes(p), "knn workspace too small");
+  const KnnWs w = knn_layout(p, ws);
+  LIDAL_REQUIRE(ws_bytes >= w.total, "knn workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)ws;
-  double* pts = (double*)base;
-  int* bounds = (int*)(base + align_up(24 * p, 256));
-  char* grid = base + align_up(24 * p, 256) + 256;
-  const int64_t gbytes = lidal_nn_grid_bytes(p);
-  char* gws = grid + align_up(gbytes, 256);
+  double* pts = w.pts;
+  int* bounds = w.bounds;
+  char* grid = w.grid;
   knn_bounds_init_kernel<<<1, 64, 0, s>>>(bounds);
   LIDAL_CHECK_LAUNCH("knn_bounds_init");
   knn_prep_kernel<<<(unsigned)cdiv(p, 256), 256, 0, s>>>(xyz, p, cell, pts, bounds);
   LIDAL_CHECK_LAUNCH("knn_prep");
-  if (int rc = lidal_nn_grid_build(pts, p, cell, grid, gbytes, gws, lidal_nn_grid_workspace_bytes(p), stream)) return rc;
+  if (int rc = lidal_nn_grid_build(pts, p, cell, grid, w.grid_bytes, w.grid_ws, w.grid_ws_bytes, stream)) return rc;
   KnnGrid g;
   const int64_t cap = table_capacity(p);
   char* gb = grid + 64;
@@ -627,7 +608,7 @@ extern "C" int lidal_region_scores(const float* prob, int64_t p, int c, const fl
 
 // ---------------------------------------------------------------- k-means
 extern "C" int64_t lidal_kmeans_workspace_bytes(int64_t n, int d, int k, int trials) {
-  return km_layout(n > 0 ? n : 1, d, k, trials, nullptr, nullptr);
+  return km_layout(n, d, k, trials, nullptr).total;
 }
 
 extern "C" int lidal_kmeans(const float* x, int64_t n, int d, int k, int64_t first, const double* u, int trials,
@@ -639,10 +620,9 @@ extern "C" int lidal_kmeans(const float* x, int64_t n, int d, int k, int64_t fir
   LIDAL_REQUIRE(trials >= 1 && trials <= 64, "kmeans: local trials must be in 1..64");
   LIDAL_REQUIRE(first >= 0 && first < n, "kmeans: first centre out of range");
   LIDAL_REQUIRE(max_iter >= 0, "kmeans: max_iter must not be negative");
-  LIDAL_REQUIRE(ws_bytes >= lidal_kmeans_workspace_bytes(n, d, k, trials), "kmeans workspace too small");
+  const KmWs w = km_layout(n, d, k, trials, ws);
+  LIDAL_REQUIRE(ws_bytes >= w.total, "kmeans workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  KmWs w;
-  km_layout(n, d, k, trials, (char*)ws, &w);
   const int64_t nc = cdiv(n, KM_CHUNK);
   const unsigned gn = (unsigned)cdiv(n, 256);
   // ---- greedy k-means++ seeding: D^2, its scan and the candidates' potentials stay on the device

@@ -378,7 +378,14 @@ supervoxel_reduce_kernel(const double* __restrict__ interd, const float* __restr
   }
 }
 
-size_t sort_pairs_tmp_bytes(int64_t p) { return (size_t)radix_sort_ws_bytes(p > 0 ? p : 1, 8, true); }
+// The one layout of lidal_nn_grid_build's scratch: it sizes with a NULL address and carves with a real one (common.h
+// Carver; the members are the regions in order).
+struct GridBuildWs { uint64_t* keys; int* idx; char* sort_tmp; int64_t sort_tmp_bytes, total; };
+GridBuildWs grid_build_layout(int64_t p, void* ws) {
+  const int64_t q = p > 0 ? p : 1, tmp = radix_sort_ws_bytes(q, 8, true);
+  Carver c(ws);
+  return {c.take<uint64_t>(q), c.take<int>(q), c.take(tmp), tmp, c.total()};
+}
 
 }  // namespace
 
@@ -399,32 +406,27 @@ extern "C" int64_t lidal_nn_grid_bytes(int64_t p) {
   return 64 + grid_off_bits(grid_cap(q), q) + grid_cap(q);
 }
 
-extern "C" int64_t lidal_nn_grid_workspace_bytes(int64_t p) {
-  int64_t q = p > 0 ? p : 1;
-  return align_up(8 * q, 256) + align_up(4 * q, 256) + align_up((int64_t)sort_pairs_tmp_bytes(q), 256);
-}
+extern "C" int64_t lidal_nn_grid_workspace_bytes(int64_t p) { return grid_build_layout(p, nullptr).total; }
 
 extern "C" int lidal_nn_grid_build(const double* pts, int64_t p, double cell, void* grid,
                                    int64_t grid_bytes, void* ws, int64_t ws_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   LIDAL_REQUIRE(cell > 0, "nn_grid_build: cell must be positive");
   LIDAL_REQUIRE(grid_bytes >= lidal_nn_grid_bytes(p), "nn grid buffer too small");
-  LIDAL_REQUIRE(ws_bytes >= lidal_nn_grid_workspace_bytes(p), "nn grid workspace too small");
+  const GridBuildWs w = grid_build_layout(p, ws);
+  LIDAL_REQUIRE(ws_bytes >= w.total, "nn grid workspace too small");
   int64_t q = p > 0 ? p : 1;
   int64_t cap = grid_cap(q);
   char* base = (char*)grid + 64;
   LIDAL_HIP(hipMemsetAsync(base, 0xFF, cap * 8, s));
   LIDAL_HIP(hipMemsetAsync(base + cap * 8, 0xFF, cap * 4, s));
   if (p == 0) return 0;
-  uint64_t* keys = (uint64_t*)ws;
-  int* idx = (int*)((char*)ws + align_up(8 * q, 256));
-  void* tmp = (char*)ws + align_up(8 * q, 256) + align_up(4 * q, 256);
   uint64_t* skeys = (uint64_t*)(base + grid_off_skeys(cap));
   int* sidx = (int*)(base + grid_off_sidx(cap, q));
   LIDAL_HIP(hipMemsetAsync(base + grid_off_bits(cap, q), 0, cap, s));
-  grid_keys_kernel<<<(unsigned)cdiv(p, 256), 256, 0, s>>>(pts, p, cell, keys, idx, (GridHeader*)grid);
+  grid_keys_kernel<<<(unsigned)cdiv(p, 256), 256, 0, s>>>(pts, p, cell, w.keys, w.idx, (GridHeader*)grid);
   LIDAL_CHECK_LAUNCH("grid_keys");
-  if (int rc = radix_sort(keys, idx, skeys, sidx, p, 8, 63, tmp, (int64_t)sort_pairs_tmp_bytes(q), s)) return rc;
+  if (int rc = radix_sort(w.keys, w.idx, skeys, sidx, p, 8, 63, w.sort_tmp, w.sort_tmp_bytes, s)) return rc;
   TableView t;
   t.keys = (unsigned long long*)base;
   t.vals = (int*)(base + cap * 8);

@@ -863,12 +863,18 @@ extern "C" int lidal_ti_weights(const float* coords, int cstride, const int64_t*
   return 0;
 }
 
-static int64_t inv_tmp_bytes(int64_t q) { return sort_pairs_ws_bytes(q); }
-
-extern "C" int64_t lidal_invlist_workspace_bytes(int64_t n_entries) {
-  int64_t q = n_entries > 0 ? n_entries : 1;
-  return 2 * align_up(4 * q, 256) + align_up(4 * q, 256) + align_up(inv_tmp_bytes(q), 256) + 256;
+// The one layout of lidal_invlist_build's scratch: it sizes with a NULL address and carves with a real one (common.h
+// Carver; the members are the regions in order, `spare` holds nothing and keeps the size what it was).
+namespace {
+struct InvlistWs { unsigned *keys, *skeys; int* vals; char *sort_tmp, *spare; int64_t sort_tmp_bytes, total; };
+InvlistWs invlist_layout(int64_t n_entries, void* ws) {
+  const int64_t q = n_entries > 0 ? n_entries : 1, tmp = sort_pairs_ws_bytes(q);
+  Carver c(ws);
+  return {c.take<unsigned>(q), c.take<unsigned>(q), c.take<int>(q), c.take(tmp), c.take(256), tmp, c.total()};
 }
+}  // namespace
+
+extern "C" int64_t lidal_invlist_workspace_bytes(int64_t n_entries) { return invlist_layout(n_entries, nullptr).total; }
 
 extern "C" int lidal_invlist_build(const int32_t* idx, const float* w, int64_t n_entries, int64_t m,
                                    int32_t* order, int64_t* seg_ptr, void* ws, int64_t ws_bytes,
@@ -879,18 +885,15 @@ extern "C" int lidal_invlist_build(const int32_t* idx, const float* w, int64_t n
     LIDAL_HIP(hipMemsetAsync(seg_ptr, 0, 8 * (m + 1), s));
     return 0;
   }
-  LIDAL_REQUIRE(ws_bytes >= lidal_invlist_workspace_bytes(n_entries), "invlist workspace too small");
+  const InvlistWs l = invlist_layout(n_entries, ws);
+  LIDAL_REQUIRE(ws_bytes >= l.total, "invlist workspace too small");
   int64_t q = n_entries;
-  unsigned* keys = (unsigned*)ws;
-  unsigned* skeys = (unsigned*)((char*)ws + align_up(4 * q, 256));
-  int* vals = (int*)((char*)ws + 2 * align_up(4 * q, 256));
-  void* tmp = (char*)ws + 3 * align_up(4 * q, 256);
-  inv_keys_kernel<<<(unsigned)cdiv(q, 256), 256, 0, s>>>(idx, w, q, m, keys, vals);
+  inv_keys_kernel<<<(unsigned)cdiv(q, 256), 256, 0, s>>>(idx, w, q, m, l.keys, l.vals);
   LIDAL_CHECK_LAUNCH("inv_keys");
   int bits = 1;
   while ((1ll << bits) <= m) ++bits;
-  if (int rc = sort_pairs_u32(keys, vals, skeys, order, q, bits, tmp, inv_tmp_bytes(q), s)) return rc;
-  inv_segptr_kernel<<<(unsigned)cdiv(m + 1, 256), 256, 0, s>>>(skeys, q, m, seg_ptr);
+  if (int rc = sort_pairs_u32(l.keys, l.vals, l.skeys, order, q, bits, l.sort_tmp, l.sort_tmp_bytes, s)) return rc;
+  inv_segptr_kernel<<<(unsigned)cdiv(m + 1, 256), 256, 0, s>>>(l.skeys, q, m, seg_ptr);
   LIDAL_CHECK_LAUNCH("inv_segptr");
   return 0;
 }
