@@ -191,7 +191,46 @@ constexpr int TILE_ROWS = 128;
 // longest tiles started last and the launch ended with a few of them alone on the chip.  Longest first is the classic
 // list-scheduling rule; as a reversal it costs nothing: 96 -> 96 at stride 1 90.2 -> 82.2-83.6 us, 32 -> 32 39.7 -> 34.8,
 // 128 -> 128 at stride 4 66.8 -> 58.7 (same results bit for bit).
-__device__ __forceinline__ int tile_of_block() { return (int)gridDim.x - 1 - (int)blockIdx.x; }
+//
+// Which COLUMN BLOCK it takes, and where (round 7).  A layer wider than a workgroup's 16 NB columns runs ny > 1 column
+// blocks per row tile; they walk the same active offsets and gather the same input rows, and differ only in the weight
+// slabs.  On the 2-D grid (PAIRED = false: x = tile reversed, y = column block) the hardware deals workgroups in linear
+// order, x fastest, round-robin over the 8 XCDs: column block y of a tile starts gridDim.x workgroups after block y - 1,
+// on whichever XCD (x + gridDim.x * y) % 8 names, and finds none of the rows its twin gathered in that XCD's L2 -- every
+// gathered row of such a layer crosses the fabric ny times.  PAIRED = true decodes a 1-D grid of 8 * ny * ceil(tiles / 8)
+// workgroups instead: linear index L = 8 * ny * g + 8 * y + lane takes column block y of the tile of rank 8 * g + lane
+// (rank 0 = the LAST tile of the row order, as above).  L % 8 == lane for every y, so the ny column blocks of a tile are
+// dealt to one XCD, 8 workgroups apart -- resident together, the later ones gathering from L2 what the first one fetched.
+// Ranks at or beyond `tiles` (the last group's padding, < 8 * ny workgroups) return at once.  With ny == 1 the decode is
+// rank == L: launch_img keeps such launches on the 2-D grid, whose instantiations are the code they were.  The placement
+// is a matter of speed alone: no result depends on which XCD, or when, a workgroup runs.
+template <bool PAIRED>
+struct WgTile {
+  int tile;                         // row tile (TILE_ROWS rows)
+  unsigned pcol, pncol, ptiles;     // PAIRED: column block, column blocks per tile, row tiles of the launch
+  // (the 2-D grid reads the hardware's indices where they are used, as before round 7: its kernels are instruction for
+  // instruction what they were)
+  __device__ __forceinline__ unsigned col() const { if constexpr (PAIRED) return pcol; else return blockIdx.y; }
+  __device__ __forceinline__ unsigned ncol() const { if constexpr (PAIRED) return pncol; else return gridDim.y; }
+  __device__ __forceinline__ unsigned tiles() const { if constexpr (PAIRED) return ptiles; else return gridDim.x; }
+  // store_tile's `n_tiles`: 0 = gridDim.x
+  __device__ __forceinline__ unsigned stats_tiles() const { if constexpr (PAIRED) return ptiles; else return 0u; }
+};
+// false: a workgroup of the last group's padding, which has no tile
+template <bool PAIRED, int BM, int BN>
+__device__ __forceinline__ bool tile_of_block(int64_t n_out, int co, WgTile<PAIRED>& t) {
+  if constexpr (!PAIRED) {
+    t.tile = (int)gridDim.x - 1 - (int)blockIdx.x;
+    return true;
+  } else {
+    const unsigned ny = (unsigned)((co + BN - 1) / BN), tiles = (unsigned)((n_out + BM - 1) / BM);
+    const unsigned L = blockIdx.x, g = L / (8u * ny), w = L - g * (8u * ny);
+    const unsigned rank = 8u * g + (w & 7u);
+    t.tile = (int)tiles - 1 - (int)rank;
+    t.pcol = w >> 3; t.pncol = ny; t.ptiles = tiles;
+    return rank < tiles;
+  }
+}
 // waves per workgroup = 128-row tiles.  16 (256-row tiles: halves the slab DMAs per row, but has no BatchNorm tile
 // statistics and no offset split) measured in round 5 (profiles/r05_lean_waves16_ab.txt: bit-equal, 9-49 % slower), not kept
 constexpr int LEAN_WAVES = 8;
@@ -199,6 +238,8 @@ constexpr int LEAN_WAVES = 8;
 // spills 52 registers: the 96 -> 96 layer 90 -> 210 us, the 5-scan step 14.7 -> 19.5 ms (measured in round 5, not kept)
 constexpr int LEAN_MINWAVES = 4;
 constexpr int64_t DEEP_MAX_ROWS = 150000;      // up to this many output rows the deep form of the lean kernel runs
+// (round 7: none of the deep kernel's shapes, nor any other, loses alone on the paired grid -- no shape keeps the 2-D
+// order for its column blocks; the measured table is at pair_columns below)
 // Optional second job of a DATA-GRADIENT launch: the tile's share of the backward sums of the BatchNorm
 // whose output gradient this launch produces (out = dy of y = act(bn(x))): per column sum(dy') and
 // sum(dy' * xhat), dy' = dy where the fused ReLU let the value through, xhat = (x - mean) * invstd -- x read
@@ -233,7 +274,9 @@ __device__ __forceinline__ void store_tile(f32x4 (&acc)[G][NB], unsigned char* w
                                            const float* __restrict__ ep_shift, int ep_relu,
                                            const T* __restrict__ ep_res, bool perm_in_reg = false,
                                            int perm_v = 0, float* __restrict__ tile_stats = nullptr,
-                                           int stats_tile = -1, const BnBwd* bnb = nullptr) {
+                                           int stats_tile = -1, const BnBwd* bnb = nullptr, unsigned n_tiles = 0u) {
+  // stats_tile / n_tiles: the workgroup's row tile and the launch's tile count as the caller decoded them
+  // (tile_of_block); without them (the combining kernel's own 2-D grid) blockIdx.x of gridDim.x
   // perm_in_reg: lane l (< 16 G) of the wave holds perm[r0 + l] in perm_v, loaded when the tile began
   // (the lean kernel: no dependent load in front of the stores)
   constexpr int VEC = DT<T>::VEC;
@@ -354,7 +397,7 @@ __device__ __forceinline__ void store_tile(f32x4 (&acc)[G][NB], unsigned char* w
       }
       // [column][tile][3] (round 5): the merge of a channel -- on the critical path of the BatchNorm launch that follows --
       // reads ONE contiguous run instead of a 12-byte piece of every tile's row (7-9 -> 3-4 us on the 397 k-row levels)
-      float* dst = tile_stats + ((int64_t)(n0 + c) * gridDim.x + (stats_tile >= 0 ? stats_tile : (int)blockIdx.x)) * 3;
+      float* dst = tile_stats + ((int64_t)(n0 + c) * (n_tiles ? n_tiles : gridDim.x) + (stats_tile >= 0 ? stats_tile : (int)blockIdx.x)) * 3;
       dst[0] = na; dst[1] = ma; dst[2] = qa;
     }
   }
@@ -411,7 +454,7 @@ __device__ __forceinline__ void store_tile(f32x4 (&acc)[G][NB], unsigned char* w
     if (c < BN && n0 + c < co) {
       float a = 0.f, b = 0.f;
       for (int w = 0; w < NWAVES; ++w) { a += st[(w * BN + c) * 2]; b += st[(w * BN + c) * 2 + 1]; }
-      float* dst = bnb->sums + ((int64_t)(n0 + c) * gridDim.x + (stats_tile >= 0 ? stats_tile : (int)blockIdx.x)) * 2;
+      float* dst = bnb->sums + ((int64_t)(n0 + c) * (n_tiles ? n_tiles : gridDim.x) + (stats_tile >= 0 ? stats_tile : (int)blockIdx.x)) * 2;
       dst[0] = a; dst[1] = b;
     }
   }
@@ -425,7 +468,7 @@ constexpr int IMG_MINWAVES = 2;
 // LDS (dynamic): ring of D+1 weight slabs (re-used as the epilogue tile) | dump 1 KiB.  The
 // neighbour indices never touch LDS: each lane loads the index of ITS row straight from the permuted
 // table (64 contiguous bytes per 16-row group) D phases ahead of the gather that uses it.
-template <typename T, int NB, int ROW_BYTES, int G, int NWAVES, int MINW, bool DENSE, int D>
+template <typename T, int NB, int ROW_BYTES, int G, int NWAVES, int MINW, bool DENSE, int D, bool PAIRED>
 __global__ void __launch_bounds__(64 * NWAVES, MINW)
 conv_apply_img_kernel(const T* __restrict__ in, const T* __restrict__ wimg,
                       const int* __restrict__ nbr, const int* __restrict__ perm,
@@ -463,9 +506,11 @@ conv_apply_img_kernel(const T* __restrict__ in, const T* __restrict__ wimg,
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int row16 = lane & 15;
   const int gsel = lane >> 4;
-  const int bx = tile_of_block();
+  WgTile<PAIRED> wg;
+  if (!tile_of_block<PAIRED, BM, BN>(n_out, co, wg)) return;
+  const int bx = wg.tile;
   const int64_t r0 = (int64_t)bx * BM + wave * RW;
-  const int n0 = blockIdx.y * BN;
+  const int n0 = wg.col() * BN;
   const int npass = (ci + KC - 1) / KC;
 
   // ---- tile mask: the OR of the 128-row masks this tile covers (scalar loads)
@@ -508,13 +553,13 @@ conv_apply_img_kernel(const T* __restrict__ in, const T* __restrict__ wimg,
       __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wimg), 0, (int)img_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_nbr =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<int*>(nbr), 0, (int)nbr_bytes, 0x00020000);
-  const int nblk = gridDim.y;
+  const int nblk = wg.ncol();
 
   // slab (k, this column block, pass) -> LDS buffer `buf` by LDS-DMA: wave w moves pieces
   // w, w + NWAVES, ...; every wave issues exactly PPW instructions (a surplus piece, or a dead
   // phase, reads out of range -- zeros, no memory traffic -- into the dump)
   auto stage_dma = [&](int k, int pass, int slot, bool live) {
-    const unsigned slab_off = (unsigned)((((int64_t)k * nblk + blockIdx.y) * npass + pass) * SLAB);
+    const unsigned slab_off = (unsigned)((((int64_t)k * nblk + wg.col()) * npass + pass) * SLAB);
 #pragma unroll
     for (int t = 0; t < PPW; ++t) {
       const int piece = wave + t * NWAVES;
@@ -662,7 +707,7 @@ conv_apply_img_kernel(const T* __restrict__ in, const T* __restrict__ wimg,
   }
 
   store_tile<T, NB, G, NWAVES>(acc, wl, wave, lane, r0, n0, n_out, co, perm, out, ep_scale, ep_shift, ep_relu,
-                               ep_res, false, 0, tile_stats, bx, &bnb);
+                               ep_res, false, 0, tile_stats, bx, &bnb, wg.stats_tiles());
 }
 
 // ------------------------------------------------------------------------------------------
@@ -702,7 +747,7 @@ __device__ unsigned long long* g_stamp_buf = nullptr;
 #define LIDAL_NOW() __builtin_readcyclecounter()
 #endif
 
-template <typename T, int NB, int ROW_BYTES, int NWAVES, bool DENSE>
+template <typename T, int NB, int ROW_BYTES, int NWAVES, bool DENSE, bool PAIRED>
 __global__ void __launch_bounds__(64 * NWAVES, (NWAVES == 8 ? LEAN_MINWAVES : 4))
 conv_lean_kernel(const T* __restrict__ in, const T* __restrict__ wimg, const int* __restrict__ nbr,
                  const int* __restrict__ perm, const unsigned* __restrict__ tmasks,
@@ -733,9 +778,11 @@ conv_lean_kernel(const T* __restrict__ in, const T* __restrict__ wimg, const int
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int row16 = lane & 15;
   const int gsel = lane >> 4;
-  const int bx = tile_of_block();
+  WgTile<PAIRED> wg;
+  if (!tile_of_block<PAIRED, BM, BN>(n_out, co, wg)) return;
+  const int bx = wg.tile;
   const int64_t r0 = (int64_t)bx * BM + wave * 16;
-  const int n0 = blockIdx.y * BN;
+  const int n0 = wg.col() * BN;
   const int npass = ci / KC;
 
   unsigned tmask = 1u;
@@ -775,8 +822,8 @@ conv_lean_kernel(const T* __restrict__ in, const T* __restrict__ wimg, const int
   const unsigned idx_voff = (unsigned)((r0 + row16) * 4);       // this row inside one offset's table row
   const bool row_in = r0 + row16 < n_out;
   const unsigned k_stride = (unsigned)n_out * 4u;               // bytes of one offset's table row
-  const unsigned slab_k = (unsigned)gridDim.y * (unsigned)npass * (unsigned)SLAB;      // slabs of one offset
-  const unsigned slab_base = (unsigned)blockIdx.y * (unsigned)npass * (unsigned)SLAB
+  const unsigned slab_k = wg.ncol() * (unsigned)npass * (unsigned)SLAB;                  // slabs of one offset
+  const unsigned slab_base = wg.col() * (unsigned)npass * (unsigned)SLAB
                              + (unsigned)(wave * PPW) * 1024u;                          // + this wave's share
   const unsigned dma_voff = (unsigned)lane * 16u;
   const bool dma_wave = wave < DMA_WAVES;
@@ -938,19 +985,19 @@ conv_lean_kernel(const T* __restrict__ in, const T* __restrict__ wimg, const int
 #undef ST_PHASE_END
   if (sp.nsplit > 1) {          // a share of the tile's offsets: the f32 accumulators go to the combining kernel
     f32x4* dst = reinterpret_cast<f32x4*>(sp.partial) +
-                 ((((int64_t)blockIdx.z * gridDim.x + bx) * gridDim.y + blockIdx.y) * NWAVES + wave) * (NB * 64) + lane;
+                 ((((int64_t)blockIdx.z * wg.tiles() + bx) * wg.ncol() + wg.col()) * NWAVES + wave) * (NB * 64) + lane;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) dst[nb * 64] = acc[0][nb];
     return;
   }
   store_tile<T, NB, 1, NWAVES>(acc, wl, wave, lane, r0, n0, n_out, co, perm, out, ep_scale, ep_shift, ep_relu,
-                               ep_res, true, perm_v, tile_stats, bx, &bnb);
+                               ep_res, true, perm_v, tile_stats, bx, &bnb, wg.stats_tiles());
 #ifdef LIDAL_PHASE_STAMPS
   if (g_stamp_buf != nullptr) {
     __builtin_amdgcn_s_waitcnt(0);                  // the tile's stores have left
     const unsigned long long st_end = LIDAL_NOW(), st_rend = __builtin_amdgcn_s_memrealtime();
     if (lane == 0) {
-      unsigned long long* d = g_stamp_buf + ((((size_t)blockIdx.y * gridDim.x + bx) * NWAVES) + wave) * 12;
+      unsigned long long* d = g_stamp_buf + ((((size_t)wg.col() * wg.tiles() + bx) * NWAVES) + wave) * 12;
       d[0] = (unsigned long long)nphase; d[1] = st_end - st_begin; d[2] = st_first - st_begin; d[3] = st_issue; d[4] = st_waita;
       d[5] = st_comp; d[6] = st_slab; d[7] = st_bar; d[8] = st_end - st_last; d[9] = st_rend - st_rbegin;
       d[10] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |                // HW_ID (wave, simd, cu, sh, se ...)
@@ -962,6 +1009,8 @@ conv_lean_kernel(const T* __restrict__ in, const T* __restrict__ wimg, const int
 }
 
 // The shares of a split launch (struct Split) added in split order, then the epilogue of the unsplit kernel.
+// Its own 2-D grid (x = row tile, y = column block) whatever grid the lean kernel ran on: it gathers nothing, and the
+// partial tiles are indexed by (split, tile, column block).
 template <typename T, int NB, int NWAVES>
 __global__ void __launch_bounds__(64 * NWAVES)
 conv_combine_kernel(Split sp, const int* __restrict__ perm, T* __restrict__ out, int64_t n_out, int co,
@@ -1006,7 +1055,7 @@ conv_combine_kernel(Split sp, const int* __restrict__ perm, T* __restrict__ out,
 // (offsets ascending, slices ascending), hence bitwise the lean kernel's results.  Used where the
 // rows are few (launch_img); on the fine levels -- gather-throughput bound, 3 resident workgroups --
 // two phases of look-ahead measured slower (round 2).
-template <typename T, int NB, int ROW_BYTES, int NWAVES, bool DENSE>
+template <typename T, int NB, int ROW_BYTES, int NWAVES, bool DENSE, bool PAIRED>
 __global__ void __launch_bounds__(64 * NWAVES, LEAN_MINWAVES)
 conv_lean_deep_kernel(const T* __restrict__ in, const T* __restrict__ wimg, const int* __restrict__ nbr,
                       const int* __restrict__ perm, const unsigned* __restrict__ tmasks,
@@ -1039,9 +1088,11 @@ conv_lean_deep_kernel(const T* __restrict__ in, const T* __restrict__ wimg, cons
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int row16 = lane & 15;
   const int gsel = lane >> 4;
-  const int bx = tile_of_block();
+  WgTile<PAIRED> wg;
+  if (!tile_of_block<PAIRED, BM, BN>(n_out, co, wg)) return;
+  const int bx = wg.tile;
   const int64_t r0 = (int64_t)bx * BM + wave * 16;
-  const int n0 = blockIdx.y * BN;
+  const int n0 = wg.col() * BN;
   const int npass = ci / KC;
 
   unsigned tmask = 1u;
@@ -1067,8 +1118,8 @@ conv_lean_deep_kernel(const T* __restrict__ in, const T* __restrict__ wimg, cons
   const unsigned idx_voff = (unsigned)((r0 + row16) * 4);
   const bool row_in = r0 + row16 < n_out;
   const unsigned k_stride = (unsigned)n_out * 4u;
-  const unsigned slab_k = (unsigned)gridDim.y * (unsigned)npass * (unsigned)SLAB;
-  const unsigned slab_base = (unsigned)blockIdx.y * (unsigned)npass * (unsigned)SLAB + (unsigned)(wave * PPW) * 1024u;
+  const unsigned slab_k = wg.ncol() * (unsigned)npass * (unsigned)SLAB;
+  const unsigned slab_base = wg.col() * (unsigned)npass * (unsigned)SLAB + (unsigned)(wave * PPW) * 1024u;
   const unsigned dma_voff = (unsigned)lane * 16u;
   const bool dma_wave = wave < DMA_WAVES;
   unsigned char* const dma_dst = wl + (wave * PPW) * 1024;
@@ -1199,7 +1250,7 @@ conv_lean_deep_kernel(const T* __restrict__ in, const T* __restrict__ wimg, cons
   __builtin_amdgcn_s_waitcnt(0x0F70);               // the dump writes of the phases past the end are done
   __syncthreads();
   store_tile<T, NB, 1, NWAVES>(acc, wl, wave, lane, r0, n0, n_out, co, perm, out, ep_scale, ep_shift, ep_relu,
-                               ep_res, true, perm_v, tile_stats, bx, &bnb);
+                               ep_res, true, perm_v, tile_stats, bx, &bnb, wg.stats_tiles());
 }
 
 
@@ -1278,9 +1329,11 @@ conv_split_kernel(const float* __restrict__ in, const __bf16* __restrict__ wimg,
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int row16 = lane & 15;
   const int gsel = lane >> 4;
-  const int bx = tile_of_block();
+  WgTile<false> wg;                                      // (the 2-D grid: this form is not on the training step's path)
+  tile_of_block<false, BM, BN>(n_out, co, wg);
+  const int bx = wg.tile;
   const int64_t r0 = (int64_t)bx * BM + wave * 16;
-  const int n0 = blockIdx.y * BN;
+  const int n0 = wg.col() * BN;
   const int npass = ci / SPLIT_KCH;
 
   unsigned tmask = 1u;
@@ -1317,8 +1370,8 @@ conv_split_kernel(const float* __restrict__ in, const __bf16* __restrict__ wimg,
   const unsigned idx_voff = (unsigned)((r0 + row16) * 4);
   const bool row_in = r0 + row16 < n_out;
   const unsigned k_stride = (unsigned)n_out * 4u;
-  const unsigned slab_k = (unsigned)gridDim.y * (unsigned)npass * (unsigned)SLAB;
-  const unsigned slab_base = (unsigned)blockIdx.y * (unsigned)npass * (unsigned)SLAB + (unsigned)(wave * PPW) * 1024u;
+  const unsigned slab_k = wg.ncol() * (unsigned)npass * (unsigned)SLAB;
+  const unsigned slab_base = wg.col() * (unsigned)npass * (unsigned)SLAB + (unsigned)(wave * PPW) * 1024u;
   const unsigned dma_voff = (unsigned)lane * 16u;
   const bool dma_wave = wave < DMA_WAVES;
   unsigned char* const dma_dst = wl + (wave * PPW) * 1024;
@@ -1443,7 +1496,7 @@ conv_split_kernel(const float* __restrict__ in, const __bf16* __restrict__ wimg,
   }
   if (sp.nsplit > 1) {          // a share of the tile's offsets: the f32 accumulators go to conv_combine_kernel
     f32x4* dst = reinterpret_cast<f32x4*>(sp.partial) +
-                 ((((int64_t)blockIdx.z * gridDim.x + bx) * gridDim.y + blockIdx.y) * NWAVES + wave) * (NB * 64) + lane;
+                 ((((int64_t)blockIdx.z * wg.tiles() + bx) * wg.ncol() + wg.col()) * NWAVES + wave) * (NB * 64) + lane;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) dst[nb * 64] = acc[0][nb];
     return;
@@ -1530,6 +1583,20 @@ __host__ inline int pick_split(int64_t wgs, int K, int npass) {
 
 constexpr int IMG_G = 1, IMG_NWAVES = 8, IMG_DEPTH = 1;       // generic kernel: row groups per wave, waves, pipeline depth
 
+// Which launches take the paired 1-D grid (tile_of_block): every one with more than one column block per row tile.
+// Measured alone on every such shape of the U-Net, forward and data gradient (scripts/exp/colblock_shapes.py,
+// profiles/README.md round 7; results bit-equal): 256 -> 256 at stride 8 (deep kernel) 106 -> 104 us, 384 -> 256 152 -> 148,
+// 256 -> 384 146 -> 134, 128 -> 256 55.6 -> 52.3, 256 -> 256 at stride 16 (four 64-column blocks) 79 -> 75, 128 -> 192 at
+// stride 4 95.8 -> 92; fabric fetches -40 to -67 %, L2 hit rate 51-77 -> 70-86 %.  None loses, so the rule has no
+// exception by (ny, n_out) -- the arguments stay for the day one is measured.  The time follows the bytes so little because
+// these launches wait for the chain of phases of their heaviest tiles (barrier + next slab), not for the fabric; the
+// step gains 0.15 ms (13.54 -> 13.39), more than the launches alone, where the fabric is shared with the side queues.
+// (pick_tiling gives NB == 2 only to co <= 32, one column block: no paired instantiation of those kernels.)
+__host__ inline bool pair_columns(unsigned ny, int64_t n_out) { (void)n_out; return ny > 1; }
+__host__ inline dim3 conv_grid(bool paired, unsigned tiles, unsigned ny) {
+  return paired ? dim3(8u * ny * ((tiles + 7u) / 8u)) : dim3(tiles, ny);
+}
+
 template <typename T, int NB, int ROW_BYTES>
 int launch_img(const void* in, const void* wimg, const int* nbr, const int* perm, const unsigned* tmasks,
                void* out, int64_t n_out, int ci, int co, int K, int kflip, Epi ep, hipStream_t s) {
@@ -1540,6 +1607,9 @@ int launch_img(const void* in, const void* wimg, const int* nbr, const int* perm
   constexpr int D = IMG_DEPTH;
   constexpr int WREGION = ((D + 1) * SLAB > EPI) ? (D + 1) * SLAB : EPI;
   static_assert(BM == TILE_ROWS, "tile masks and BatchNorm statistics triples are per 128-row tile");
+  constexpr bool CAN_PAIR = NB > 2;
+  const unsigned tiles = (unsigned)cdiv(n_out, BM), ny = (unsigned)cdiv(co, BN);
+  const bool paired = CAN_PAIR && pair_columns(ny, n_out);
   if constexpr (G == 1 && NWAVES == 8) {
     if (ci % (ROW_BYTES / (int)sizeof(T)) == 0 && ep.in_bytes / ((unsigned)ci * sizeof(T)) < (1u << 24)) {
       constexpr int LW = LEAN_WAVES;
@@ -1560,15 +1630,16 @@ int launch_img(const void* in, const void* wimg, const int* nbr, const int* perm
 #endif
         constexpr int DEPI = LEPI + LSTATS;
         constexpr int DEEP_LDS = ((3 * SLAB > DEPI) ? 3 * SLAB : DEPI) + 4096;
-        auto dk = conv_lean_deep_kernel<T, NB, ROW_BYTES, LW, false>;
-        static size_t deep_attr[MAX_DEVICES] = {};
+        auto dk = paired ? conv_lean_deep_kernel<T, NB, ROW_BYTES, LW, false, CAN_PAIR>
+                         : conv_lean_deep_kernel<T, NB, ROW_BYTES, LW, false, false>;
+        static size_t deep_attr[2][MAX_DEVICES] = {};
         const int ddev = current_device();
-        if (deep_attr[ddev] < (size_t)DEEP_LDS) {
+        if (deep_attr[paired][ddev] < (size_t)DEEP_LDS) {
           LIDAL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dk),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, DEEP_LDS));
-          deep_attr[ddev] = DEEP_LDS;
+          deep_attr[paired][ddev] = DEEP_LDS;
         }
-        dim3 dgrid((unsigned)cdiv(n_out, LBM), (unsigned)cdiv(co, BN));
+        const dim3 dgrid = conv_grid(paired, tiles, ny);
         dk<<<dgrid, 64 * LW, DEEP_LDS, s>>>((const T*)in, (const T*)wimg, nbr, perm, tmasks, (T*)out, n_out,
                                             ci, co, K, kflip, ep.scale, ep.shift, ep.relu, (const T*)ep.res,
                                             ep.in_bytes, ep.img_bytes, ep.nbr_bytes, ep.tile_stats, ep.bnb);
@@ -1576,16 +1647,18 @@ int launch_img(const void* in, const void* wimg, const int* nbr, const int* perm
         return 0;
        }
       }
-      auto lk = nbr ? conv_lean_kernel<T, NB, ROW_BYTES, LW, false>
-                    : conv_lean_kernel<T, NB, ROW_BYTES, LW, true>;
-      static size_t lean_attr[2][MAX_DEVICES] = {};
-      const int ldev = current_device();
-      if (lean_attr[nbr ? 0 : 1][ldev] < (size_t)LEAN_LDS) {
+      auto lk = paired ? (nbr ? conv_lean_kernel<T, NB, ROW_BYTES, LW, false, CAN_PAIR>
+                              : conv_lean_kernel<T, NB, ROW_BYTES, LW, true, CAN_PAIR>)
+                       : (nbr ? conv_lean_kernel<T, NB, ROW_BYTES, LW, false, false>
+                              : conv_lean_kernel<T, NB, ROW_BYTES, LW, true, false>);
+      static size_t lean_attr[4][MAX_DEVICES] = {};
+      const int ldev = current_device(), lsel = (nbr ? 0 : 1) + (paired ? 2 : 0);
+      if (lean_attr[lsel][ldev] < (size_t)LEAN_LDS) {
         LIDAL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lk),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, LEAN_LDS));
-        lean_attr[nbr ? 0 : 1][ldev] = LEAN_LDS;
+        lean_attr[lsel][ldev] = LEAN_LDS;
       }
-      dim3 lgrid((unsigned)cdiv(n_out, LBM), (unsigned)cdiv(co, BN));
+      dim3 lgrid(tiles, ny);                 // the combining kernel's grid; the lean kernel's is conv_grid()
       Split sp{nullptr, 1, 0, 0};
       // (bf16 only: the f32 parity mode keeps ONE f32 sum over the offsets per output element, the association its
       // golden gradients were taken with -- through 49 train-mode BatchNorm layers a last-bit change of a sum moves
@@ -1597,8 +1670,9 @@ int launch_img(const void* in, const void* wimg, const int* nbr, const int* perm
         if (ns > 1 && ep.ws_bytes >= (long long)ns * rows_pad * co_pad * 4)
           sp = Split{(float*)ep.ws, ns, co_pad, rows_pad};
       }
-      lgrid.z = (unsigned)sp.nsplit;
-      lk<<<lgrid, 64 * LW, LEAN_LDS, s>>>((const T*)in, (const T*)wimg, nbr, perm, tmasks, (T*)out, n_out,
+      dim3 kgrid = conv_grid(paired, tiles, ny);
+      kgrid.z = (unsigned)sp.nsplit;
+      lk<<<kgrid, 64 * LW, LEAN_LDS, s>>>((const T*)in, (const T*)wimg, nbr, perm, tmasks, (T*)out, n_out,
                                           ci, co, K, kflip, ep.scale, ep.shift, ep.relu, (const T*)ep.res,
                                           ep.in_bytes, ep.img_bytes, ep.nbr_bytes, ep.tile_stats, ep.bnb, sp);
       LIDAL_CHECK_LAUNCH("lidal_conv_apply_image(lean)");
@@ -1611,7 +1685,6 @@ int launch_img(const void* in, const void* wimg, const int* nbr, const int* perm
                                         hipFuncAttributeMaxDynamicSharedMemorySize, COMB_LDS));
           comb_attr[ldev] = COMB_LDS;
         }
-        lgrid.z = 1;
         ck<<<lgrid, 64 * LW, COMB_LDS, s>>>(sp, perm, (T*)out, n_out, co, ep.scale, ep.shift, ep.relu,
                                             (const T*)ep.res, ep.tile_stats, ep.bnb);
         LIDAL_CHECK_LAUNCH("lidal_conv_apply_image(combine)");
@@ -1620,16 +1693,18 @@ int launch_img(const void* in, const void* wimg, const int* nbr, const int* perm
     }
   }
   const size_t lds = WREGION + 1024 + NWAVES * BN * 2 * sizeof(float);
-  auto kern = nbr ? conv_apply_img_kernel<T, NB, ROW_BYTES, G, NWAVES, IMG_MINWAVES, false, D>
-                  : conv_apply_img_kernel<T, NB, ROW_BYTES, G, NWAVES, IMG_MINWAVES, true, D>;
-  static size_t attr_set[2][MAX_DEVICES] = {};
-  const int dev = current_device();
-  if (attr_set[nbr ? 0 : 1][dev] < lds) {
+  auto kern = paired ? (nbr ? conv_apply_img_kernel<T, NB, ROW_BYTES, G, NWAVES, IMG_MINWAVES, false, D, CAN_PAIR>
+                            : conv_apply_img_kernel<T, NB, ROW_BYTES, G, NWAVES, IMG_MINWAVES, true, D, CAN_PAIR>)
+                     : (nbr ? conv_apply_img_kernel<T, NB, ROW_BYTES, G, NWAVES, IMG_MINWAVES, false, D, false>
+                            : conv_apply_img_kernel<T, NB, ROW_BYTES, G, NWAVES, IMG_MINWAVES, true, D, false>);
+  static size_t attr_set[4][MAX_DEVICES] = {};
+  const int dev = current_device(), sel = (nbr ? 0 : 1) + (paired ? 2 : 0);
+  if (attr_set[sel][dev] < lds) {
     LIDAL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set[nbr ? 0 : 1][dev] = lds;
+    attr_set[sel][dev] = lds;
   }
-  dim3 grid((unsigned)cdiv(n_out, BM), (unsigned)cdiv(co, BN));
+  const dim3 grid = conv_grid(paired, tiles, ny);
   kern<<<grid, NTHREADS, lds, s>>>((const T*)in, (const T*)wimg, nbr, perm, tmasks, (T*)out, n_out, ci,
                                    co, K, kflip, ep.scale, ep.shift, ep.relu, (const T*)ep.res,
                                    ep.in_bytes, ep.img_bytes, ep.nbr_bytes, ep.tile_stats, ep.bnb);
