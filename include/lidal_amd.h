@@ -621,6 +621,45 @@ int lidal_kmeans(const float* x, int64_t n, int d, int k, int64_t first, const d
                  double tol, int32_t* seeds, int32_t* labels, double* centers, double* inertia_host,
                  int32_t* n_iter_host, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- size-constrained k-means supervoxels (dataset/prepare_supervoxel_kmeans_{sk,nu}.py; csrc/supervoxel.hip;
+ *      DESIGN.md section 11) ------------------------------------------------------------------------------------ */
+/* Error words of the balanced assignment (status[2 f]; 0: none).  Nothing retries: the caller raises. */
+enum {
+  LIDAL_FLOW_INFEASIBLE = 1,  /* k * size_min > p, k * size_max < p, or size_min outside 0..size_max */
+  LIDAL_FLOW_NO_TARGET = 2,   /* no deficit node can be reached */
+  LIDAL_FLOW_WALK = 3,        /* the walk back along the parents does not end at an excess node in k steps */
+  LIDAL_FLOW_NOT_SETTLED = 4, /* the distances still change after k + 1 rounds (a negative cycle) */
+  LIDAL_FLOW_NO_POINT = 5     /* an arc of the path has no point */
+};
+/* The integer arc costs: cost i32 [p,k] = rint(1000 * sqrt((dx*dx + dy*dy) + dz*dz)) in f64, every product and sum
+ * rounded, ties to even; xyz f32 [p,3] widened against centers f64 [k,3].  1 <= k <= 64; finite coordinates of
+ * magnitude below 5e5 keep the cost inside an int32 (not checked here: lidal_amd.data does). */
+int lidal_supervoxel_costs(const float* xyz, int64_t p, const double* centers, int k, int32_t* cost, void* stream);
+/* The exact least-cost labels with every cluster size in [size_min, size_max], for a batch of frames in one launch (one
+ * workgroup per frame, successive shortest paths on the k + 1 node cluster graph).  cost i32 [p_total, k] (row p of
+ * frame f at frame_ptr[f] + p), frame_ptr i64 [n_frames + 1], size_min / size_max i32 [n_frames]: all on the device;
+ * 1 <= k <= 64.  Out (device): labels i32 [p_total], counts i32 [n_frames, k] (the cluster sizes; may be NULL),
+ * objective i64 [n_frames] (the sum of cost[p][labels[p]]), status i32 [n_frames, 2] = (error word, augmentations).
+ * A frame with an error word keeps the labels it had reached.  Workspace: lidal_balanced_assign_workspace_bytes. */
+int64_t lidal_balanced_assign_workspace_bytes(int64_t p_total, int n_frames, int k);
+int lidal_balanced_assign(const int32_t* cost, const int64_t* frame_ptr, int n_frames, int64_t p_total, int k,
+                          const int32_t* size_min, const int32_t* size_max, int32_t* labels, int32_t* counts,
+                          int64_t* objective, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
+/* The whole definition for a batch of frames: per frame the greedy k-means++ seeds of lidal_kmeans (from row first[f]
+ * with the uniforms u f64 [n_frames, (k-1) * trials] on the device), costs rint(1000 * distance) to the seed rows, a
+ * balanced assignment, the centre update of lidal_kmeans, costs again and a second balanced assignment.  xyz f32
+ * [p_total, 3] (device); frame_ptr, size_min, size_max, first: HOST arrays.  Out (device): seeds i32 [n_frames, k],
+ * labels_first i32 [p_total], centers f64 [n_frames, k, 3] (the updated ones), labels i32 [p_total], order i32 [p_total]
+ * (per frame its point ids sorted by (label, point)), counts i32 [n_frames, k] (of `labels`), objective i64
+ * [2, n_frames], status i32 [2, n_frames, 2] (first, second assignment).  Does not synchronise the stream.
+ * Workspace: lidal_supervoxel_kmeans_workspace_bytes(p_total, the largest frame, n_frames, k, trials). */
+int64_t lidal_supervoxel_kmeans_workspace_bytes(int64_t p_total, int64_t p_max, int n_frames, int k, int trials);
+int lidal_supervoxel_kmeans(const float* xyz, const int64_t* frame_ptr_host, int n_frames, int k,
+                            const int32_t* size_min_host, const int32_t* size_max_host, const int64_t* first_host,
+                            const double* u, int trials, int32_t* seeds, int32_t* labels_first, double* centers,
+                            int32_t* labels, int32_t* order, int32_t* counts, int64_t* objective, int32_t* status,
+                            void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- frame-level selection (score/frame_level/ of the reference; csrc/frame_level.hip) ---------------------- */
 /* softmax_entropy.py, margin_sampling.py, least_confidence_sampling.py worker_func for one frame, prob f32 [p,c]
  * (2 <= c <= 32): out f32 [3] = (np.mean(entropy(prob, axis=1)), np.mean(top1 - top2), np.mean(top1)), numpy's

@@ -149,6 +149,12 @@ SIGNATURES = {
     'lidal_kmeans_workspace_bytes': (_i64, [_i64, _i32, _i32, _i32]),
     'lidal_kmeans': (_i32, [_vp, _i64, _i32, _i32, _i64, _vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                             _vp]),
+    'lidal_supervoxel_costs': (_i32, [_vp, _i64, _vp, _i32, _vp, _vp]),
+    'lidal_balanced_assign_workspace_bytes': (_i64, [_i64, _i32, _i32]),
+    'lidal_balanced_assign': (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'lidal_supervoxel_kmeans_workspace_bytes': (_i64, [_i64, _i64, _i32, _i32, _i32]),
+    'lidal_supervoxel_kmeans': (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _i64, _vp]),
     'lidal_frame_uncertainty_workspace_bytes': (_i64, [_i64]),
     'lidal_frame_uncertainty': (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _vp]),
     'lidal_segment_entropy_workspace_bytes': (_i64, [_i32]),

@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "grid.h"
+#include "kmeans.h"
 #include "npsum.h"
 
 using namespace lidal;
@@ -456,22 +457,7 @@ __global__ void km_starts_kernel(const int* __restrict__ counts, int k, int* __r
 }
 
 // Workspace layouts: one function per builder sizes its scratch (NULL address) and carves it (common.h Carver; the
-// members are the regions in order).
-struct KmWs {
-  double *closest, *D, *cs, *tot, *off, *pot_t, *pot, *mind2, *cnew, *shift;
-  int *cand, *best, *old, *keys, *iota, *skeys, *order, *counts, *starts, *changed;
-  char* sort_tmp;
-  int64_t sort_bytes, total;
-};
-KmWs km_layout(int64_t n_rows, int d, int k, int trials, void* ws) {
-  const int64_t n = n_rows > 0 ? n_rows : 1, nc = cdiv(n, KM_CHUNK), tr = trials > 0 ? trials : 1;
-  const int64_t tmp = radix_sort_ws_bytes(n, 4, true);
-  Carver c(ws);
-  return {c.take<double>(n), c.take<double>(n * tr), c.take<double>(n), c.take<double>(nc * tr), c.take<double>(nc * tr),
-          c.take<double>(tr), c.take<double>(1), c.take<double>(n), c.take<double>((int64_t)k * d), c.take<double>(1),
-          c.take<int>(tr), c.take<int>(1), c.take<int>(n), c.take<int>(n), c.take<int>(n), c.take<int>(n), c.take<int>(n),
-          c.take<int>(k), c.take<int>(k), c.take<int>(1), c.take(tmp), tmp, c.total()};
-}
+// members are the regions in order).  The k-means one is kmeans.h's km_layout, below.
 
 // k-NN: the points as f64, the cell bounds of the scan, the search grid and the scratch of its build
 struct KnnWs { double* pts; int* bounds; char *grid, *grid_ws; int64_t grid_bytes, grid_ws_bytes, total; };
@@ -531,6 +517,70 @@ int km_total(const double* v, int64_t n, const KmWs& w, hipStream_t s, double* o
 }
 
 }  // namespace
+
+
+// ---------------------------------------------------------------- k-means steps shared with supervoxel.hip (kmeans.h)
+namespace lidal {
+
+KmWs km_layout(int64_t n_rows, int d, int k, int trials, void* ws) {
+  const int64_t n = n_rows > 0 ? n_rows : 1, nc = cdiv(n, KM_CHUNK), tr = trials > 0 ? trials : 1;
+  const int64_t tmp = radix_sort_ws_bytes(n, 4, true);
+  Carver c(ws);
+  return {c.take<double>(n), c.take<double>(n * tr), c.take<double>(n), c.take<double>(nc * tr), c.take<double>(nc * tr),
+          c.take<double>(tr), c.take<double>(1), c.take<double>(n), c.take<double>((int64_t)k * d), c.take<double>(1),
+          c.take<int>(tr), c.take<int>(1), c.take<int>(n), c.take<int>(n), c.take<int>(n), c.take<int>(n), c.take<int>(n),
+          c.take<int>(k), c.take<int>(k), c.take<int>(1), c.take(tmp), tmp, c.total()};
+}
+
+int km_seed(const float* x, int64_t n, int d, int k, int64_t first, const double* u, int trials, int32_t* seeds,
+            double* centers, const KmWs& w, hipStream_t s) {
+  const int64_t nc = cdiv(n, KM_CHUNK);
+  const unsigned gn = (unsigned)cdiv(n, 256);
+  km_first_seed_kernel<<<1, 64, 0, s>>>(seeds, (int)first);
+  LIDAL_CHECK_LAUNCH("km_first_seed");
+  km_first_kernel<<<gn, 256, 0, s>>>(x, n, d, first, w.closest);
+  LIDAL_CHECK_LAUNCH("km_first");
+  if (int rc = km_total(w.closest, n, w, s, w.pot)) return rc;
+  for (int c = 1; c < k; ++c) {
+    km_scan_apply_kernel<<<(unsigned)cdiv(nc, 256), 256, 0, s>>>(w.closest, n, w.off, c == 1 ? nullptr : w.best, w.cs);
+    LIDAL_CHECK_LAUNCH("km_scan_apply");
+    km_search_kernel<<<1, 64, 0, s>>>(w.cs, n, w.pot, u + (int64_t)(c - 1) * trials, trials, w.cand);
+    LIDAL_CHECK_LAUNCH("km_search");
+    km_trial_kernel<<<gn, 256, 0, s>>>(x, n, d, w.cand, trials, w.closest, w.D);
+    LIDAL_CHECK_LAUNCH("km_trial");
+    km_chunk_sums_kernel<<<(unsigned)cdiv(nc * trials, 256), 256, 0, s>>>(w.D, n, trials, w.tot);
+    LIDAL_CHECK_LAUNCH("km_chunk_sums");
+    km_offsets_kernel<<<1, 64, 0, s>>>(w.tot, nc, trials, w.off, w.pot_t);
+    LIDAL_CHECK_LAUNCH("km_offsets");
+    km_pick_kernel<<<1, 64, 0, s>>>(w.pot_t, trials, w.cand, c, w.best, seeds, w.pot);
+    LIDAL_CHECK_LAUNCH("km_pick");
+    km_take_kernel<<<gn, 256, 0, s>>>(w.D, n, w.best, w.closest);
+    LIDAL_CHECK_LAUNCH("km_take");
+  }
+  km_gather_kernel<<<(unsigned)cdiv((int64_t)k * d, 256), 256, 0, s>>>(x, d, seeds, k, centers);
+  LIDAL_CHECK_LAUNCH("km_gather");
+  return 0;
+}
+
+int km_iota(int64_t n, const KmWs& w, hipStream_t s) {
+  km_iota_kernel<<<(unsigned)cdiv(n, 256), 256, 0, s>>>(w.iota, n);
+  LIDAL_CHECK_LAUNCH("km_iota");
+  return 0;
+}
+
+int km_update(const float* x, int64_t n, int d, int k, const int32_t* labels, const int* counts, const double* centers,
+              double* out, const KmWs& w, hipStream_t s) {
+  int end_bit = 1;
+  while ((1 << end_bit) < k) ++end_bit;
+  if (int rc = radix_sort(labels, w.iota, w.skeys, w.order, n, 4, end_bit, w.sort_tmp, w.sort_bytes, s)) return rc;
+  km_starts_kernel<<<1, 64, 0, s>>>(counts, k, w.starts);
+  LIDAL_CHECK_LAUNCH("km_starts");
+  km_update_kernel<<<(unsigned)cdiv((int64_t)k * d, 256), 256, 0, s>>>(x, d, k, w.order, w.starts, counts, centers, out);
+  LIDAL_CHECK_LAUNCH("km_update");
+  return 0;
+}
+
+}  // namespace lidal
 
 // ---------------------------------------------------------------- k-NN / surface variation
 extern "C" int64_t lidal_knn_workspace_bytes(int64_t p) { return knn_layout(p, nullptr).total; }
@@ -623,38 +673,11 @@ extern "C" int lidal_kmeans(const float* x, int64_t n, int d, int k, int64_t fir
   const KmWs w = km_layout(n, d, k, trials, ws);
   LIDAL_REQUIRE(ws_bytes >= w.total, "kmeans workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int64_t nc = cdiv(n, KM_CHUNK);
   const unsigned gn = (unsigned)cdiv(n, 256);
-  // ---- greedy k-means++ seeding: D^2, its scan and the candidates' potentials stay on the device
-  km_first_seed_kernel<<<1, 64, 0, s>>>(seeds, (int)first);
-  LIDAL_CHECK_LAUNCH("km_first_seed");
-  km_first_kernel<<<gn, 256, 0, s>>>(x, n, d, first, w.closest);
-  LIDAL_CHECK_LAUNCH("km_first");
-  if (int rc = km_total(w.closest, n, w, s, w.pot)) return rc;
-  for (int c = 1; c < k; ++c) {
-    km_scan_apply_kernel<<<(unsigned)cdiv(nc, 256), 256, 0, s>>>(w.closest, n, w.off, c == 1 ? nullptr : w.best, w.cs);
-    LIDAL_CHECK_LAUNCH("km_scan_apply");
-    km_search_kernel<<<1, 64, 0, s>>>(w.cs, n, w.pot, u + (int64_t)(c - 1) * trials, trials, w.cand);
-    LIDAL_CHECK_LAUNCH("km_search");
-    km_trial_kernel<<<gn, 256, 0, s>>>(x, n, d, w.cand, trials, w.closest, w.D);
-    LIDAL_CHECK_LAUNCH("km_trial");
-    km_chunk_sums_kernel<<<(unsigned)cdiv(nc * trials, 256), 256, 0, s>>>(w.D, n, trials, w.tot);
-    LIDAL_CHECK_LAUNCH("km_chunk_sums");
-    km_offsets_kernel<<<1, 64, 0, s>>>(w.tot, nc, trials, w.off, w.pot_t);
-    LIDAL_CHECK_LAUNCH("km_offsets");
-    km_pick_kernel<<<1, 64, 0, s>>>(w.pot_t, trials, w.cand, c, w.best, seeds, w.pot);
-    LIDAL_CHECK_LAUNCH("km_pick");
-    km_take_kernel<<<gn, 256, 0, s>>>(w.D, n, w.best, w.closest);
-    LIDAL_CHECK_LAUNCH("km_take");
-  }
-  km_gather_kernel<<<(unsigned)cdiv((int64_t)k * d, 256), 256, 0, s>>>(x, d, seeds, k, centers);
-  LIDAL_CHECK_LAUNCH("km_gather");
+  if (int rc = km_seed(x, n, d, k, first, u, trials, seeds, centers, w, s)) return rc;
   // ---- Lloyd
-  km_iota_kernel<<<gn, 256, 0, s>>>(w.iota, n);
-  LIDAL_CHECK_LAUNCH("km_iota");
+  if (int rc = km_iota(n, w, s)) return rc;
   LIDAL_HIP(hipMemsetAsync(w.old, 0xFF, 4 * (size_t)n, s));         // labels_old = -1
-  int end_bit = 1;
-  while ((1 << end_bit) < k) ++end_bit;
   bool strict = false;
   int it = 0;
   for (; it < max_iter; ++it) {
@@ -663,12 +686,7 @@ extern "C" int lidal_kmeans(const float* x, int64_t n, int d, int k, int64_t fir
     LIDAL_HIP(hipMemsetAsync(w.changed, 0, 4, s));
     km_changed_kernel<<<gn, 256, 0, s>>>(labels, w.old, n, w.changed);
     LIDAL_CHECK_LAUNCH("km_changed");
-    if (int rc = radix_sort(labels, w.iota, w.skeys, w.order, n, 4, end_bit, w.sort_tmp, w.sort_bytes, s)) return rc;
-    km_starts_kernel<<<1, 64, 0, s>>>(w.counts, k, w.starts);
-    LIDAL_CHECK_LAUNCH("km_starts");
-    km_update_kernel<<<(unsigned)cdiv((int64_t)k * d, 256), 256, 0, s>>>(x, d, k, w.order, w.starts, w.counts, centers,
-                                                                          w.cnew);
-    LIDAL_CHECK_LAUNCH("km_update");
+    if (int rc = km_update(x, n, d, k, labels, w.counts, centers, w.cnew, w, s)) return rc;
     km_shift_kernel<<<1, 256, 0, s>>>(w.cnew, centers, (int64_t)k * d, w.shift);
     LIDAL_CHECK_LAUNCH("km_shift");
     LIDAL_HIP(hipMemcpyAsync(centers, w.cnew, 8 * (size_t)k * d, hipMemcpyDeviceToDevice, s));

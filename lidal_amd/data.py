@@ -11,6 +11,11 @@ Training labels (sk_dataset.py:106-141,170-171; nu_dataset.py:128-160,189-190; D
 the raw annotation words, the round's supervoxel flags, the supervoxel membership lists and last round's predictions
 into labels_p / labels_v in lidal_train_labels, and `train_sample` composes the three steps into the dict `collate`
 takes.  The frame filters of the loaders (`labeled_frames`, `frames_from_flag`) stay on the host: they pick files.
+
+Supervoxels (dataset/prepare_supervoxel_kmeans_{sk,nu}.py): `kmeans_supervoxels` clusters raw scans
+into size-constrained k-means supervoxels in lidal_supervoxel_kmeans and returns the labels with the device CSR the
+scorers and `train_labels` take; `supervoxel_tables` turns the labels into the (sv_id, sv2point) pickles and the id2sv
+list of an existing Processing_files tree; `balanced_assign` is the exact size-constrained assignment on its own.
 """
 import math
 
@@ -21,7 +26,8 @@ from . import backend as B
 
 __all__ = ['draw_augmentation', 'voxelize_scan', 'collate', 'parse_calibration', 'parse_poses',
            'register_scan', 'sk_label_map', 'nu_label_map', 'train_labels', 'train_sample', 'check_labels',
-           'labeled_frames', 'frames_from_flag']
+           'labeled_frames', 'frames_from_flag', 'kmeans_supervoxels', 'supervoxel_tables', 'balanced_assign',
+           'supervoxel_bounds', 'supervoxel_costs']
 
 SCALE = 20                # sk_dataset.py:56
 FULL_SCALE = 8192
@@ -292,3 +298,200 @@ def register_scan(points, pose):
     B.check(B.lib().lidal_register_points(B.ptr(points), p, B.ptr(pose_dev), B.ptr(world), B.stream()),
             'register_points')
     return world
+
+
+# ---- size-constrained k-means supervoxels (dataset/prepare_supervoxel_kmeans_sk.py) ---------
+SV_KMAX = 64              # csrc/supervoxel.hip: one bit per cluster in the 64-bit masks
+SV_REACH = 5e5            # metres: 1000 * the largest distance between two points stays inside an int32 cost
+_FLOW_ERRORS = {1: 'the size bounds admit no assignment', 2: 'no deficit node can be reached',
+                3: 'the path walk does not end at an excess node', 4: 'the distances did not settle',
+                5: 'an arc of the path has no point'}
+
+
+def supervoxel_bounds(p, n_clusters=20, slack=0.05):
+    """(size_min, size_max) of prepare_supervoxel_kmeans_sk.py:17 for a scan of p points: int(p / k * 0.95) and
+    int(p / k * 1.05) in Python floats."""
+    return int(p / n_clusters * (1 - slack)), int(p / n_clusters * (1 + slack))
+
+
+def _check_bounds(p, k, lo, hi, what):
+    if not 1 <= k <= SV_KMAX:
+        raise ValueError('%s: n_clusters=%d must be in 1..%d' % (what, k, SV_KMAX))
+    if p < k:
+        raise ValueError('%s: %d points for %d clusters' % (what, p, k))
+    if lo < 0 or lo > hi or k * hi < p or k * lo > p:
+        raise ValueError('%s: no assignment of %d points to %d clusters has every size in [%d, %d]'
+                         % (what, p, k, lo, hi))
+
+
+def _raise_flow_errors(status, what):
+    """status: host i32 [..., n_frames, 2] = (error word, augmentations)."""
+    bad = np.argwhere(status[..., 0] != 0)
+    if len(bad):
+        where = tuple(int(v) for v in bad[0])
+        code = int(status[where + (0,)])
+        raise RuntimeError('%s: frame %d: %s (error word %d)' % (what, where[-1], _FLOW_ERRORS.get(code, '?'), code))
+
+
+def _finite_points(xyz, what):
+    reach = float(xyz.abs().max()) if xyz.numel() else 0.0      # (NaN if any coordinate is; one synchronisation)
+    if not reach < float('inf'):
+        raise ValueError('%s: the coordinates must be finite (NaN or inf found)' % what)
+    if not reach < SV_REACH:
+        raise ValueError('%s: a coordinate of magnitude %g does not fit the integer costs (limit %g)'
+                         % (what, reach, SV_REACH))
+
+
+def supervoxel_costs(xyz, centers):
+    """The integer arc costs of the definition: xyz f32 [P,3] and centers f64 [K,3] on the GPU -> int32 [P,K],
+    rint(1000 * distance) with the distance in f64 as numpy rounds it."""
+    B.require_gpu(xyz, centers)
+    xyz = xyz.float().contiguous()
+    centers = centers.double().contiguous()
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or centers.ndim != 2 or centers.shape[1] != 3:
+        raise ValueError('supervoxel_costs: xyz [P, 3] and centers [K, 3]')
+    p, k = xyz.shape[0], centers.shape[0]
+    if not 1 <= k <= SV_KMAX:
+        raise ValueError('supervoxel_costs: %d centres (1..%d)' % (k, SV_KMAX))
+    _finite_points(xyz, 'supervoxel_costs')
+    _finite_points(centers, 'supervoxel_costs')
+    cost = torch.empty((p, k), dtype=torch.int32, device=xyz.device)
+    B.check(B.lib().lidal_supervoxel_costs(B.ptr(xyz), p, B.ptr(centers), k, B.ptr(cost), B.stream()),
+            'supervoxel_costs')
+    return cost
+
+
+def balanced_assign(cost, size_min, size_max):
+    """The exact least-cost assignment of P points to K <= 64 clusters with every cluster size in
+    [size_min, size_max]: cost int32 [P,K] on the GPU (or a list of such frames, with one bound each or one pair for
+    all) -> (labels i64 [P] on the GPU, objective) per frame.  Ties: DESIGN.md section 11.  Infeasible bounds raise
+    ValueError before anything is launched; an error word of the kernel raises RuntimeError."""
+    single = torch.is_tensor(cost)
+    frames = [cost] if single else list(cost)
+    n = len(frames)
+    lo = [int(v) for v in (size_min if isinstance(size_min, (list, tuple)) else [size_min] * n)]
+    hi = [int(v) for v in (size_max if isinstance(size_max, (list, tuple)) else [size_max] * n)]
+    if n == 0 or len(lo) != n or len(hi) != n:
+        raise ValueError('balanced_assign: %d frames, %d / %d bounds' % (n, len(lo), len(hi)))
+    k = frames[0].shape[1] if frames[0].ndim == 2 else 0
+    for c, l, h in zip(frames, lo, hi):
+        if c.dtype != torch.int32 or c.ndim != 2 or c.shape[1] != k:
+            raise TypeError('balanced_assign: cost must be int32 [P, K] with one K for all frames')
+        _check_bounds(c.shape[0], k, l, h, 'balanced_assign')
+    B.require_gpu(*frames)
+    dev = frames[0].device
+    ptr = np.concatenate([[0], np.cumsum([c.shape[0] for c in frames])]).astype(np.int64)
+    p_total = int(ptr[-1])
+    cost_all = frames[0].contiguous() if n == 1 else torch.cat([c.contiguous() for c in frames])
+    ptr_dev = torch.from_numpy(ptr).to(dev)
+    lo_dev = torch.tensor(lo, dtype=torch.int32, device=dev)
+    hi_dev = torch.tensor(hi, dtype=torch.int32, device=dev)
+    labels = torch.empty(p_total, dtype=torch.int32, device=dev)
+    objective = torch.empty(n, dtype=torch.int64, device=dev)
+    status = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    nbytes = B.lib().lidal_balanced_assign_workspace_bytes(p_total, n, k)
+    ws = B.workspace(nbytes, dev)
+    B.check(B.lib().lidal_balanced_assign(B.ptr(cost_all), B.ptr(ptr_dev), n, p_total, k, B.ptr(lo_dev), B.ptr(hi_dev),
+                                          B.ptr(labels), None, B.ptr(objective), B.ptr(status), B.ptr(ws), nbytes,
+                                          B.stream()), 'balanced_assign')
+    _raise_flow_errors(status.cpu().numpy(), 'balanced_assign')
+    obj = objective.cpu().numpy()
+    out = [(labels[ptr[f]:ptr[f + 1]].long(), int(obj[f])) for f in range(n)]
+    return out[0] if single else out
+
+
+def kmeans_supervoxels(points, n_clusters=20, slack=0.05, random_state=0, details=False):
+    """Size-constrained k-means supervoxels of raw scans on the GPU, in place of prepare_supervoxel_kmeans_sk.py:17-18
+    (KMeansConstrained(n_clusters, size_min, size_max, n_init=1, max_iter=1, random_state).fit_predict) as this project
+    defines it: greedy k-means++ seeds, integer costs rint(1000 * distance), an exact
+    size-constrained assignment, one centre update, and the assignment again.
+
+    points: f32 [P,3] on the GPU, or a list of such scans (one batch of launches).  Returns per scan
+    (labels i64 [P], sv_ptr i64 [S+1], sv_idx i64 [P]) on the GPU: the labels, and the supervoxel CSR in the form of
+    score.interframe.sv_csr (supervoxels in label order, empty clusters dropped, point ids ascending), which
+    score_frame, region_scores, segment_entropy and train_labels take as it is.  details=True appends a dict with
+    seeds, labels_first, centers, counts, objective (first, second), augmentations (first, second), size_min, size_max.
+    Raises ValueError, before any launch, for n_clusters outside 1..64, fewer points than clusters, size bounds no
+    assignment can meet (21 points in 20 clusters: size_max is 1) and coordinates that are not finite."""
+    from .score.redal import kmeans_draws
+    single = torch.is_tensor(points)
+    frames = [points] if single else list(points)
+    if not frames:
+        raise ValueError('kmeans_supervoxels: no scans')
+    k = int(n_clusters)
+    lo, hi = [], []
+    for x in frames:
+        if x.ndim != 2 or x.shape[1] != 3:
+            raise ValueError('kmeans_supervoxels: points must be [P, 3], not %s' % (tuple(x.shape),))
+        l, h = supervoxel_bounds(x.shape[0], k, slack) if 1 <= k <= SV_KMAX else (0, 0)
+        _check_bounds(x.shape[0], k, l, h, 'kmeans_supervoxels')
+        lo.append(l), hi.append(h)
+    B.require_gpu(*frames)
+    frames = [x.float().contiguous() for x in frames]
+    xyz = frames[0] if len(frames) == 1 else torch.cat(frames)
+    _finite_points(xyz, 'kmeans_supervoxels')
+    n = len(frames)
+    dev = xyz.device
+    seed = int(np.random.RandomState(random_state).randint(2 ** 31 - 1, size=1)[0])
+    draws = [kmeans_draws(x.shape[0], k, seed) for x in frames]
+    trials = draws[0][2]
+    first = np.array([d[0] for d in draws], dtype=np.int64)
+    u = np.concatenate([d[1].reshape(-1) for d in draws] + [np.zeros(1)])
+    u_dev = torch.from_numpy(u).to(dev)
+    ptr = np.concatenate([[0], np.cumsum([x.shape[0] for x in frames])]).astype(np.int64)
+    p_total, p_max = int(ptr[-1]), int(max(x.shape[0] for x in frames))
+    lo_h, hi_h = np.array(lo, dtype=np.int32), np.array(hi, dtype=np.int32)
+    seeds = torch.empty((n, k), dtype=torch.int32, device=dev)
+    labels_first = torch.empty(p_total, dtype=torch.int32, device=dev)
+    centers = torch.empty((n, k, 3), dtype=torch.float64, device=dev)
+    labels = torch.empty(p_total, dtype=torch.int32, device=dev)
+    order = torch.empty(p_total, dtype=torch.int32, device=dev)
+    counts = torch.empty((n, k), dtype=torch.int32, device=dev)
+    objective = torch.empty((2, n), dtype=torch.int64, device=dev)
+    status = torch.empty((2, n, 2), dtype=torch.int32, device=dev)
+    nbytes = B.lib().lidal_supervoxel_kmeans_workspace_bytes(p_total, p_max, n, k, trials)
+    ws = B.workspace(nbytes, dev)
+    B.check(B.lib().lidal_supervoxel_kmeans(B.ptr(xyz), ptr.ctypes.data, n, k, lo_h.ctypes.data, hi_h.ctypes.data,
+                                            first.ctypes.data, B.ptr(u_dev), trials, B.ptr(seeds), B.ptr(labels_first),
+                                            B.ptr(centers), B.ptr(labels), B.ptr(order), B.ptr(counts),
+                                            B.ptr(objective), B.ptr(status), B.ptr(ws), nbytes, B.stream()),
+            'supervoxel_kmeans')
+    host = torch.cat([status.reshape(-1), counts.reshape(-1)]).cpu().numpy()        # the one read-back
+    status_h, counts_h = host[:4 * n].reshape(2, n, 2), host[4 * n:].reshape(n, k)
+    _raise_flow_errors(status_h, 'kmeans_supervoxels')
+    objective_h = objective.cpu().numpy() if details else None
+    out = []
+    for f in range(n):
+        a, b = int(ptr[f]), int(ptr[f + 1])
+        sizes = counts_h[f][counts_h[f] > 0].astype(np.int64)
+        sv_ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)).to(dev)
+        item = (labels[a:b].long(), sv_ptr, order[a:b].long())
+        if details:
+            item += (dict(seeds=seeds[f], labels_first=labels_first[a:b].long(), centers=centers[f], counts=counts[f],
+                          objective=(int(objective_h[0, f]), int(objective_h[1, f])),
+                          augmentations=(int(status_h[0, f, 1]), int(status_h[1, f, 1])),
+                          size_min=lo[f], size_max=hi[f]),)
+        out.append(item)
+    return out[0] if single else out
+
+
+def supervoxel_tables(labels_per_frame, frame_names):
+    """prepare_supervoxel_kmeans_sk.py:54-80 on host arrays: the per-frame supervoxel labels (arrays or tensors, in
+    the order of the sorted label files) and their (sequence, frame name) pairs -> (tables, id2sv): per frame
+    (sv_id i64 [S], sv2point list of i64 arrays) as io.save_supervoxels writes them -- supervoxels in np.unique(labels)
+    order with ascending point ids, a cluster without points dropped, sv_id running across the frames -- and the
+    id2sv list of (sequence, frame name, supervoxel of the frame) that io.save_id2sv writes."""
+    if len(labels_per_frame) != len(frame_names):
+        raise ValueError('%d label arrays for %d frame names' % (len(labels_per_frame), len(frame_names)))
+    tables, id2sv, next_id = [], [], 0
+    for lab, (seq, name) in zip(labels_per_frame, frame_names):
+        lab = lab.detach().cpu().numpy() if torch.is_tensor(lab) else np.asarray(lab)
+        lab = lab.reshape(-1)
+        order = np.argsort(lab, kind='stable')                    # by (label, point)
+        values, starts = np.unique(lab[order], return_index=True)
+        sv2point = [part.astype(np.int64) for part in np.split(order, starts[1:])] if len(values) else []
+        sv_id = np.arange(len(sv2point), dtype=np.int64) + next_id
+        next_id += len(sv2point)
+        tables.append((sv_id, sv2point))
+        id2sv.extend((seq, name, local) for local in np.arange(len(sv2point)))
+    return tables, id2sv

@@ -7,6 +7,10 @@ vice versa.
   pred/.../<frame>.npy         i64 [P]       score/prob_inference.py:130
   super_voxel/.../<frame>.pickle (sv_id i64 [S], sv2point list of i64 arrays)
                                               dataset/prepare_supervoxel_kmeans_sk.py:62-74
+  super_voxel/KMeans/<seq>/<frame>.npy        [P] the cluster of every point (`clf.labels_`)
+                                              dataset/prepare_supervoxel_kmeans_sk.py:21-22
+  super_voxel/KMeans/id2sv.pickle             list of (sequence, frame name, supervoxel of the frame), by sv_id
+                                              dataset/prepare_supervoxel_kmeans_sk.py:77-80
   sv_flag/.../<frame>.npy      i64 [S] in {0,1,2}   LiDAL.py:328-330
   super_voxel/KMeans/sv_pnums.npy, sv_centers.npy   i64 [sum S]; f32 [sum S, 3] with the
                                +1000 * sequence-index offset      LiDAL.py:173-177,220-222
@@ -27,7 +31,8 @@ import pickle
 import numpy as np
 import torch
 
-__all__ = ['save_prob_pred', 'load_prob', 'load_supervoxels', 'save_supervoxels', 'load_sv_flag',
+__all__ = ['save_prob_pred', 'load_prob', 'load_supervoxels', 'save_supervoxels', 'save_sv_labels', 'load_sv_labels',
+           'save_id2sv', 'load_id2sv', 'load_sv_flag',
            'save_sv_flag', 'load_sv_stats', 'save_sv_stats', 'load_curvature', 'save_curvature', 'frame_flag_path', 'load_frame_flag',
            'save_frame_flag', 'save_checkpoint', 'load_checkpoint', 'load_scan', 'load_labels', 'load_pred']
 
@@ -65,6 +70,35 @@ def save_supervoxels(path, sv_id, sv2point):
     _mkdir_for(path)
     with open(path, 'wb') as f:
         pickle.dump((np.asarray(sv_id), [np.asarray(p) for p in sv2point]), f)
+
+
+def save_sv_labels(path, labels):
+    """The cluster of every point of one scan (lidal_amd.data.kmeans_supervoxels' labels, a tensor or an array) ->
+    super_voxel/KMeans/<seq>/<frame>.npy, the file prepare_supervoxel_kmeans_sk.py:21-22 writes from `clf.labels_`
+    (int32, scikit-learn's label type)."""
+    labels = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    _mkdir_for(path)
+    np.save(path, labels.reshape(-1).astype(np.int32))
+
+
+def load_sv_labels(path):
+    """-> i64 [P], read as prepare_supervoxel_kmeans_sk.py:59 reads it."""
+    labels = np.load(path)
+    assert labels.ndim == 1 and labels.dtype.kind in 'iu', (labels.dtype, labels.shape)
+    return labels.astype(np.int64)
+
+
+def save_id2sv(path, id2sv):
+    """The list of (sequence, frame name, supervoxel of the frame) indexed by sv_id -> super_voxel/KMeans/id2sv.pickle
+    (prepare_supervoxel_kmeans_sk.py:77-80)."""
+    _mkdir_for(path)
+    with open(path, 'wb') as f:
+        pickle.dump(list(id2sv), f)
+
+
+def load_id2sv(path):
+    with open(path, 'rb') as f:
+        return [tuple(entry) for entry in pickle.load(f)]
 
 
 def load_sv_flag(path):
