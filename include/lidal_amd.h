@@ -660,6 +660,32 @@ int lidal_supervoxel_kmeans(const float* xyz, const int64_t* frame_ptr_host, int
                             int32_t* labels, int32_t* order, int32_t* counts, int64_t* objective, int32_t* status,
                             void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- VCCS supervoxels (dataset/prepare_supervoxel_VCCS_{sk,nu}.py, which pipe every scan through a PCL program;
+ *      csrc/vccs.hip; DESIGN.md section 12: this project's definition, not the library's labels) ------------------- */
+/* Error words (status[0]; 0: none).  Nothing retries: the caller raises. */
+enum {
+  LIDAL_VCCS_CELL_RANGE = 1,   /* a cell or seed cell does not fit 21 bits per axis */
+  LIDAL_VCCS_NO_SLOT = 2,      /* an occupied cell is not found among the voxels' keys */
+  LIDAL_VCCS_NO_CANDIDATE = 3  /* a seed cell without a voxel */
+};
+/* A batch of scans in one chain of launches: xyz f32 [p_total, 3] (device), frame_ptr HOST i64 [n_frames + 1].  Voxels
+ * are numbered across the batch, frame after frame, in (x, y, z) order of their cells; so are the supervoxels, in
+ * (x, y, z) order of their seed cells.  Out (device; every per-voxel and per-supervoxel array has p_total rows, of
+ * which the first V resp. S are written): labels i64 [p_total] (1.. inside the frame, 0: none), point_voxel i32
+ * [p_total], cells i32 [.,3], qs i64 [.,3] (sums of rint(x * 65536)), nv i32 [.], centroids f64 [.,3], normals f64
+ * [.,3], seed_voxels i32 [.] (the voxel of supervoxel s), owners i32 [.] (the voxels' labels), order i32 [p_total] (the
+ * batch's points sorted by (frame, label, point)), counts i32 [.] (points per supervoxel), status i64
+ * [4 + 2 (n_frames + 1)] = {error word, V, seed cells, S, first voxel of every frame and V, first supervoxel of every
+ * frame and S}.  min_seed and rounds come from the host (lidal_amd.data).  1 <= points per frame < 2^24, fewer than
+ * 2^31 / 27 points in the batch (the 27-offset table is indexed by an int).  Does not synchronise the stream.
+ * Workspace: lidal_vccs_workspace_bytes(p_total, n_frames). */
+int64_t lidal_vccs_workspace_bytes(int64_t p_total, int n_frames);
+int lidal_vccs(const float* xyz, const int64_t* frame_ptr_host, int n_frames, double voxel_resolution,
+               double seed_resolution, double spatial_importance, double normal_importance, double min_seed, int rounds,
+               int64_t* labels, int32_t* point_voxel, int32_t* cells, int64_t* qs, int32_t* nv, double* centroids,
+               double* normals, int32_t* seed_voxels, int32_t* owners, int32_t* order, int32_t* counts, int64_t* status,
+               void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- frame-level selection (score/frame_level/ of the reference; csrc/frame_level.hip) ---------------------- */
 /* softmax_entropy.py, margin_sampling.py, least_confidence_sampling.py worker_func for one frame, prob f32 [p,c]
  * (2 <= c <= 32): out f32 [3] = (np.mean(entropy(prob, axis=1)), np.mean(top1 - top2), np.mean(top1)), numpy's

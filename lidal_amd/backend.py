@@ -155,6 +155,9 @@ SIGNATURES = {
     'lidal_supervoxel_kmeans_workspace_bytes': (_i64, [_i64, _i64, _i32, _i32, _i32]),
     'lidal_supervoxel_kmeans': (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _i64, _vp]),
+    'lidal_vccs_workspace_bytes': (_i64, [_i64, _i32]),
+    'lidal_vccs': (_i32, [_vp, _vp, _i32, _f64, _f64, _f64, _f64, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                          _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'lidal_frame_uncertainty_workspace_bytes': (_i64, [_i64]),
     'lidal_frame_uncertainty': (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _vp]),
     'lidal_segment_entropy_workspace_bytes': (_i64, [_i32]),

@@ -475,12 +475,116 @@ def kmeans_supervoxels(points, n_clusters=20, slack=0.05, random_state=0, detail
     return out[0] if single else out
 
 
-def supervoxel_tables(labels_per_frame, frame_names):
+# ---- VCCS supervoxels (dataset/prepare_supervoxel_VCCS_sk.py) --------------------------------
+_VCCS_ERRORS = {1: 'a cell does not fit 21 bits per axis', 2: 'an occupied cell was not found among the voxels',
+                3: 'a seed cell has no voxel'}
+
+
+def vccs_parameters(voxel_resolution=0.5, seed_resolution=10.0):
+    """(min_seed, rounds) of the definition, in Python floats: the least number of voxels within half a seed resolution
+    a seed candidate must exceed (15.7 at the defaults), and the number of synchronous rounds (35)."""
+    rv, rs = float(voxel_resolution), float(seed_resolution)
+    return 0.05 * (0.5 * rs) ** 2 * math.pi / rv ** 2, int(1.8 * rs / rv) - 1
+
+
+def _check_vccs(frames, rv, rs, w_s, w_n):
+    if not frames:
+        raise ValueError('vccs_supervoxels: no scans')
+    if not (rv > 0 and math.isfinite(rv) and math.isfinite(rs)):
+        raise ValueError('vccs_supervoxels: voxel_resolution=%r must be positive and finite' % rv)
+    if rs < 2 * rv:
+        raise ValueError('vccs_supervoxels: seed_resolution=%r is below two voxels of %r' % (rs, rv))
+    if SV_REACH / rv >= 2 ** 20:
+        raise ValueError('vccs_supervoxels: cells of %r m do not fit 21 bits per axis over +-%g m' % (rv, SV_REACH))
+    if not (w_s >= 0 and w_n >= 0 and math.isfinite(w_s) and math.isfinite(w_n)):
+        raise ValueError('vccs_supervoxels: the importances must not be negative')
+    for x in frames:
+        if not torch.is_tensor(x) or x.ndim != 2 or x.shape[1] != 3:
+            raise ValueError('vccs_supervoxels: points must be [P, 3], not %s' % (tuple(getattr(x, 'shape', ())),))
+        if x.shape[0] == 0:
+            raise ValueError('vccs_supervoxels: a scan without points')
+        if x.shape[0] >= 2 ** 24:
+            raise ValueError('vccs_supervoxels: %d points in one scan (at most 2^24 - 1)' % x.shape[0])
+    if sum(x.shape[0] for x in frames) >= 2 ** 31 // 27:
+        raise ValueError('vccs_supervoxels: %d points in one batch (fewer than %d)'
+                         % (sum(x.shape[0] for x in frames), 2 ** 31 // 27))
+
+
+def vccs_supervoxels(points, voxel_resolution=0.5, seed_resolution=10.0, spatial_importance=0.4, normal_importance=1.0,
+                     min_points=100, details=False):
+    """VCCS supervoxels of raw scans on the GPU, in place of prepare_supervoxel_VCCS_sk.py:17-28 (every scan piped
+    through pcl::SupervoxelClustering<PointXYZ>(0.5, 10.0) with spatial importance 0.4 and normal importance 1.0) as
+    this project defines them.  The PCL library's labels are not reproduced.
+
+    points: f32 [P,3] on the GPU, or a list of such scans (one batch of launches).  Returns per scan
+    (labels i64 [P], sv_ptr i64 [S+1], sv_idx i64) on the GPU: label 0 is "no supervoxel"; the CSR holds the labels
+    != 0 with strictly more than min_points points, in label order with ascending point ids
+    (prepare_supervoxel_VCCS_sk.py:72-77), in the form score_frame, region_scores, segment_entropy and train_labels
+    take.  details=True appends a dict with cells, centroids, normals, point_voxel, qs, n, seed_voxels, owners, counts,
+    rounds, min_seed.  Raises ValueError before any launch for what the definition refuses."""
+    single = torch.is_tensor(points)
+    frames = [points] if single else list(points)
+    rv, rs = float(voxel_resolution), float(seed_resolution)
+    w_s, w_n = float(spatial_importance), float(normal_importance)
+    _check_vccs(frames, rv, rs, w_s, w_n)
+    for x in frames:
+        _finite_points(x, 'vccs_supervoxels')
+    B.require_gpu(*frames)
+    frames = [x.float().contiguous() for x in frames]
+    xyz = frames[0] if len(frames) == 1 else torch.cat(frames)
+    min_seed, rounds = vccs_parameters(rv, rs)
+    n, dev = len(frames), xyz.device
+    ptr = np.concatenate([[0], np.cumsum([x.shape[0] for x in frames])]).astype(np.int64)
+    p = int(ptr[-1])
+    i32 = dict(dtype=torch.int32, device=dev)
+    labels = torch.empty(p, dtype=torch.int64, device=dev)
+    point_voxel, cells, nv = torch.empty(p, **i32), torch.empty((p, 3), **i32), torch.empty(p, **i32)
+    qs = torch.empty((p, 3), dtype=torch.int64, device=dev)
+    cen = torch.empty((p, 3), dtype=torch.float64, device=dev)
+    nrm = torch.empty((p, 3), dtype=torch.float64, device=dev)
+    seed_voxels, owners, order, counts = (torch.empty(p, **i32) for _ in range(4))
+    status = torch.empty(4 + 2 * (n + 1), dtype=torch.int64, device=dev)
+    nbytes = B.lib().lidal_vccs_workspace_bytes(p, n)
+    ws = B.workspace(nbytes, dev)
+    B.check(B.lib().lidal_vccs(B.ptr(xyz), ptr.ctypes.data, n, rv, rs, w_s, w_n, min_seed, rounds, B.ptr(labels),
+                               B.ptr(point_voxel), B.ptr(cells), B.ptr(qs), B.ptr(nv), B.ptr(cen), B.ptr(nrm),
+                               B.ptr(seed_voxels), B.ptr(owners), B.ptr(order), B.ptr(counts), B.ptr(status), B.ptr(ws),
+                               nbytes, B.stream()), 'vccs')
+    host = torch.cat([status, counts.long()]).cpu().numpy()                    # the one read-back
+    st, counts_h = host[:status.numel()], host[status.numel():]
+    if st[0] != 0:
+        raise RuntimeError('vccs_supervoxels: %s (error word %d)' % (_VCCS_ERRORS.get(int(st[0]), '?'), int(st[0])))
+    vptr, sptr = st[4:4 + n + 1], st[4 + n + 1:4 + 2 * (n + 1)]
+    out = []
+    for f in range(n):
+        a, b = int(ptr[f]), int(ptr[f + 1])
+        v0, v1, s0, s1 = int(vptr[f]), int(vptr[f + 1]), int(sptr[f]), int(sptr[f + 1])
+        sizes = counts_h[s0:s1]
+        keep = sizes > min_points
+        starts = (b - a) - int(sizes.sum()) + np.concatenate([[0], np.cumsum(sizes)[:-1]]) if s1 > s0 else sizes
+        local = order[a:b].long() - a                          # the scan's points by (label, point); label 0 first
+        parts = [local[int(t):int(t) + int(c)] for t, c in zip(starts[keep], sizes[keep])]
+        sv_idx = torch.cat(parts) if parts else torch.empty(0, dtype=torch.int64, device=dev)
+        sv_ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes[keep])]).astype(np.int64)).to(dev)
+        item = (labels[a:b], sv_ptr, sv_idx)
+        if details:
+            item += (dict(cells=cells[v0:v1], centroids=cen[v0:v1], normals=nrm[v0:v1], qs=qs[v0:v1], n=nv[v0:v1],
+                          point_voxel=point_voxel[a:b].long() - v0, seed_voxels=seed_voxels[s0:s1].long() - v0,
+                          owners=owners[v0:v1].long(), counts=counts[s0:s1], rounds=rounds, min_seed=min_seed),)
+        out.append(item)
+    return out[0] if single else out
+
+
+def supervoxel_tables(labels_per_frame, frame_names, ignore_label=None, min_points=0):
     """prepare_supervoxel_kmeans_sk.py:54-80 on host arrays: the per-frame supervoxel labels (arrays or tensors, in
     the order of the sorted label files) and their (sequence, frame name) pairs -> (tables, id2sv): per frame
     (sv_id i64 [S], sv2point list of i64 arrays) as io.save_supervoxels writes them -- supervoxels in np.unique(labels)
     order with ascending point ids, a cluster without points dropped, sv_id running across the frames -- and the
-    id2sv list of (sequence, frame name, supervoxel of the frame) that io.save_id2sv writes."""
+    id2sv list of (sequence, frame name, supervoxel of the frame) that io.save_id2sv writes.
+
+    ignore_label=0, min_points=100 gives prepare_supervoxel_VCCS_sk.py:58-92: label 0 ("no supervoxel") is dropped and
+    so is every supervoxel of min_points points or fewer; the supervoxels that stay are numbered 0.. inside the frame
+    in label order.  The defaults drop nothing."""
     if len(labels_per_frame) != len(frame_names):
         raise ValueError('%d label arrays for %d frame names' % (len(labels_per_frame), len(frame_names)))
     tables, id2sv, next_id = [], [], 0
@@ -490,6 +594,9 @@ def supervoxel_tables(labels_per_frame, frame_names):
         order = np.argsort(lab, kind='stable')                    # by (label, point)
         values, starts = np.unique(lab[order], return_index=True)
         sv2point = [part.astype(np.int64) for part in np.split(order, starts[1:])] if len(values) else []
+        if ignore_label is not None or min_points > 0:
+            sv2point = [part for value, part in zip(values, sv2point)
+                        if (ignore_label is None or value != ignore_label) and len(part) > min_points]
         sv_id = np.arange(len(sv2point), dtype=np.int64) + next_id
         next_id += len(sv2point)
         tables.append((sv_id, sv2point))

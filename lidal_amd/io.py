@@ -11,6 +11,8 @@ vice versa.
                                               dataset/prepare_supervoxel_kmeans_sk.py:21-22
   super_voxel/KMeans/id2sv.pickle             list of (sequence, frame name, supervoxel of the frame), by sv_id
                                               dataset/prepare_supervoxel_kmeans_sk.py:77-80
+  super_voxel/VCCS/...                        the same three formats (dataset/prepare_supervoxel_VCCS_sk.py:27-28,
+                                              79-92): the functions of the KMeans tree serve it, nothing is VCCS-only
   sv_flag/.../<frame>.npy      i64 [S] in {0,1,2}   LiDAL.py:328-330
   super_voxel/KMeans/sv_pnums.npy, sv_centers.npy   i64 [sum S]; f32 [sum S, 3] with the
                                +1000 * sequence-index offset      LiDAL.py:173-177,220-222
