@@ -16,8 +16,6 @@ using namespace lidal::npsum;
 
 namespace {
 
-constexpr int FL_MAXC = 32;
-
 // scipy.special.entr on an f32 value: -x * log(x) evaluated in double and rounded once; entr(0) = 0, entr(x < 0) = -inf
 __device__ __forceinline__ float entr_f32(float x) {
   if (isnan(x)) return x;
@@ -36,11 +34,11 @@ __global__ void __launch_bounds__(256) point_uncertainty_kernel(const float* __r
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p) return;
   const float* row = prob + i * c;
-  const float s = np_leaf_f32([&](int64_t t) { return row[t]; }, 0, c);
-  float term[FL_MAXC];
+  const float s = np_sum_f32(row, c);
+  float term[kMaxClasses];
   float t1 = -INFINITY, t2 = -INFINITY;
 #pragma unroll
-  for (int j = 0; j < FL_MAXC; ++j)
+  for (int j = 0; j < kMaxClasses; ++j)
     if (j < c) {
       const float v = row[j];
       term[j] = entr_f32(__fdiv_rn(v, s));
@@ -56,7 +54,7 @@ __global__ void __launch_bounds__(256) point_uncertainty_kernel(const float* __r
   out[2 * p + i] = t1;
 }
 
-// numpy's f32 add-reduce of one block of at most 8192 contiguous values (np_mean_f32's inner walk), in parallel: lane 0
+// numpy's f32 add-reduce of one block of at most 8192 contiguous values (npsum.h's np_block_walk), in parallel: lane 0
 // walks the pairwise tree once and writes its leaves (at most 128: every leaf below a split holds more than 64 values)
 // and the post-order of the additions to LDS, one lane sums each leaf, lane 0 combines the leaf sums in the walk's
 // order.  Block b of series k (blockIdx = (b, k)) reads src[k * stride + b * 8192 ..) and writes sums[k * nb + b].
@@ -77,35 +75,18 @@ __global__ void __launch_bounds__(MEAN_LANES) block_sum_kernel(const float* __re
   const int64_t b0 = b * NP_BUFSIZE;
   const int64_t m = std::min<int64_t>(NP_BUFSIZE, n - b0);
   if (tid == 0) {
-    int sp = 1, nl = 0, np_ = 0;
-    st_off[0] = b0; st_n[0] = m; st_phase[0] = 0;
-    while (sp > 0) {
-      const int top = sp - 1;
-      const int64_t o = st_off[top], len = st_n[top];
-      if (len <= 128) {
-        leaf_off[nl] = o; leaf_n[nl] = (int)len;
-        prog[np_++] = (short)nl++;
-        --sp;
-        continue;
-      }
-      int64_t h = len / 2;
-      h -= h % 8;
-      if (st_phase[top] == 0) {
-        st_phase[top] = 1;
-        st_off[sp] = o; st_n[sp] = h; st_phase[sp] = 0; ++sp;
-      } else if (st_phase[top] == 1) {
-        st_phase[top] = 2;
-        st_off[sp] = o + h; st_n[sp] = len - h; st_phase[sp] = 0; ++sp;
-      } else {
-        prog[np_++] = -1;
-        --sp;
-      }
-    }
+    int nl = 0, np_ = 0;
+    np_block_walk(b0, m, st_off, st_n, st_phase,
+                  [&](int64_t o, int64_t len) {
+                    leaf_off[nl] = o; leaf_n[nl] = (int)len;
+                    prog[np_++] = (short)nl++;
+                  },
+                  [&] { prog[np_++] = -1; });
     n_leaves = nl;
     n_prog = np_;
   }
   __syncthreads();
-  if (tid < n_leaves) leaf_val[tid] = np_leaf_f32([&](int64_t t) { return a[t]; }, leaf_off[tid], leaf_n[tid]);
+  if (tid < n_leaves) leaf_val[tid] = np_leaf_f32([&](int64_t t) { return a[t]; }, leaf_off[tid], (int64_t)leaf_n[tid]);
   __syncthreads();
   if (tid != 0) return;
   int vp = 0;
@@ -348,7 +329,8 @@ extern "C" int64_t lidal_frame_uncertainty_workspace_bytes(int64_t p) { return u
 
 extern "C" int lidal_frame_uncertainty(const float* prob, int64_t p, int c, float* out, void* ws, int64_t ws_bytes,
                                        void* stream) {
-  LIDAL_REQUIRE(c >= 2 && c <= FL_MAXC, "frame_uncertainty: classes must be in 2..%d (the margin needs two)", FL_MAXC);
+  LIDAL_REQUIRE(c >= 2 && c <= kMaxClasses, "frame_uncertainty: classes must be in 2..%d (the margin needs two)",
+                kMaxClasses);
   LIDAL_REQUIRE(p >= 0, "frame_uncertainty: negative point count");
   const UncertaintyWs w = uncertainty_layout(p, ws);
   LIDAL_REQUIRE(ws_bytes >= w.total, "frame_uncertainty workspace too small");

@@ -1,6 +1,6 @@
-// The two k-means steps that redal.hip (lidal_kmeans) and supervoxel.hip (lidal_supervoxel_kmeans) share: the greedy
+// The two k-means steps that kmeans.hip (lidal_kmeans) and supervoxel.hip (lidal_supervoxel_kmeans) share: the greedy
 // k-means++ seeding and the deterministic centre update, with the workspace they carve (DESIGN.md sections 8 and 11).
-// Defined in redal.hip.
+// Defined in kmeans.hip.
 #pragma once
 
 #include "common.h"

@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "grid.h"
+#include "npsum.h"
 
 // The reference computes these quantities with numpy (separately rounded products and sums); hipcc
 // contracts a*b+c into fma even through __dmul_rn/__dadd_rn, so this unit is built with
@@ -16,30 +17,9 @@
 
 using namespace lidal;
 using namespace lidal::grid;
+using namespace lidal::npsum;
 
 namespace {
-
-constexpr int MAXC = 32;    // classes (19 SemanticKITTI, 16 nuScenes)
-
-// numpy's pairwise float32 add-reduce of n <= 128 contiguous values (n = number of classes)
-__device__ __forceinline__ float np_sum_f32(const float* a, int n) {
-  if (n < 8) {
-    float r = 0.f;
-    for (int i = 0; i < n; ++i) r = __fadd_rn(r, a[i]);
-    return r;
-  }
-  float r[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = a[j];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = __fadd_rn(r[j], a[i + j]);
-  float res = __fadd_rn(__fadd_rn(__fadd_rn(r[0], r[1]), __fadd_rn(r[2], r[3])),
-                        __fadd_rn(__fadd_rn(r[4], r[5]), __fadd_rn(r[6], r[7])));
-  for (; i < n; ++i) res = __fadd_rn(res, a[i]);
-  return res;
-}
 
 // ---------------- view-mean softmax ----------------
 __global__ void __launch_bounds__(256) view_mean_softmax_kernel(const float* __restrict__ logits,
@@ -49,29 +29,29 @@ __global__ void __launch_bounds__(256) view_mean_softmax_kernel(const float* __r
                                                                 int64_t* __restrict__ pred) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p) return;
-  float acc[MAXC];
+  float acc[kMaxClasses];
 #pragma unroll
-  for (int j = 0; j < MAXC; ++j) acc[j] = 0.f;
+  for (int j = 0; j < kMaxClasses; ++j) acc[j] = 0.f;
   for (int v = 0; v < reps; ++v) {
     const float* row = logits + inverse[(int64_t)v * p + i] * c;
-    float x[MAXC];
+    float x[kMaxClasses];
     float mx = -INFINITY;
 #pragma unroll
-    for (int j = 0; j < MAXC; ++j)
+    for (int j = 0; j < kMaxClasses; ++j)
       if (j < c) { x[j] = row[j]; mx = fmaxf(mx, x[j]); }
     float s = 0.f;
 #pragma unroll
-    for (int j = 0; j < MAXC; ++j)
+    for (int j = 0; j < kMaxClasses; ++j)
       if (j < c) { x[j] = expf(x[j] - mx); s += x[j]; }
 #pragma unroll
-    for (int j = 0; j < MAXC; ++j)
+    for (int j = 0; j < kMaxClasses; ++j)
       if (j < c) acc[j] = (v == 0) ? (x[j] / s) : __fadd_rn(acc[j], x[j] / s);
   }
   float best = -INFINITY;
   int arg = 0;
   const float inv = (float)reps;
 #pragma unroll
-  for (int j = 0; j < MAXC; ++j)
+  for (int j = 0; j < kMaxClasses; ++j)
     if (j < c) {
       float m = acc[j] / inv;
       prob[i * c + j] = m;
@@ -88,7 +68,7 @@ __global__ void __launch_bounds__(256) confusion_kernel(const float* __restrict_
                                                         const int64_t* __restrict__ inverse,
                                                         const int64_t* __restrict__ labels,
                                                         int64_t p, int c, int* __restrict__ conf) {
-  __shared__ int hist[MAXC * MAXC];
+  __shared__ int hist[kMaxClasses * kMaxClasses];
   for (int i = threadIdx.x; i < c * c; i += 256) hist[i] = 0;
   __syncthreads();
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -296,9 +276,9 @@ interframe_kernel(const float* __restrict__ q_prob, int64_t p, int c, NeiArgs ne
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= p) return;
   const int64_t i = q_order != nullptr ? (int64_t)q_order[t] : t;       // (match[] is in thread order)
-  float q[MAXC], sum[MAXC];
+  float q[kMaxClasses], sum[kMaxClasses];
 #pragma unroll
-  for (int j = 0; j < MAXC; ++j) {
+  for (int j = 0; j < kMaxClasses; ++j) {
     q[j] = (j < c) ? q_prob[i * c + j] : 0.f;
     sum[j] = q[j];
   }
@@ -309,9 +289,9 @@ interframe_kernel(const float* __restrict__ q_prob, int64_t p, int c, NeiArgs ne
     const int j = match[(int64_t)n * p + t];
     if (j < 0) continue;
     const float* np = nei.prob[n] + (int64_t)j * c;
-    float term[MAXC];
+    float term[kMaxClasses];
 #pragma unroll
-    for (int k = 0; k < MAXC; ++k)
+    for (int k = 0; k < kMaxClasses; ++k)
       if (k < c) {
         float nv = np[k];
         sum[k] = __fadd_rn(sum[k], nv);
@@ -323,15 +303,15 @@ interframe_kernel(const float* __restrict__ q_prob, int64_t p, int c, NeiArgs ne
     cnt += 1;
   }
   // sum_prob /= map_count (f64 divide, f32 store); entropy = scipy.stats.entropy(sum_prob)
-  float pk[MAXC];
+  float pk[kMaxClasses];
   const double mc = (double)(cnt + 1);
 #pragma unroll
-  for (int k = 0; k < MAXC; ++k)
+  for (int k = 0; k < kMaxClasses; ++k)
     if (k < c) pk[k] = (float)((double)sum[k] / mc);
   float tot = np_sum_f32(pk, c);
-  float ent[MAXC];
+  float ent[kMaxClasses];
 #pragma unroll
-  for (int k = 0; k < MAXC; ++k)
+  for (int k = 0; k < kMaxClasses; ++k)
     if (k < c) {
       float v = pk[k] / tot;
       ent[k] = (v > 0.f) ? (float)(-(double)v * log((double)v)) : 0.f;
@@ -392,7 +372,7 @@ GridBuildWs grid_build_layout(int64_t p, void* ws) {
 extern "C" int lidal_view_mean_softmax(const float* logits, const int64_t* inverse, int reps,
                                        int64_t p, int c, float* prob, int64_t* pred,
                                        void* stream) {
-  LIDAL_REQUIRE(c > 0 && c <= MAXC, "view_mean_softmax: classes must be in 1..%d", MAXC);
+  LIDAL_REQUIRE(c > 0 && c <= kMaxClasses, "view_mean_softmax: classes must be in 1..%d", kMaxClasses);
   LIDAL_REQUIRE(reps > 0, "view_mean_softmax: reps must be positive");
   if (p == 0) return 0;
   view_mean_softmax_kernel<<<(unsigned)cdiv(p, 256), 256, 0, (hipStream_t)stream>>>(
@@ -448,7 +428,7 @@ static int interframe_score(const double* q_pts, const float* q_prob, int64_t p,
                             int n_nei, double dis_thresh, double* interd, float* intere,
                             int32_t* map_count, void* ws, int64_t ws_bytes, const void* q_grid,
                             void* stream) {
-  LIDAL_REQUIRE(c > 0 && c <= MAXC, "interframe_score: classes must be in 1..%d", MAXC);
+  LIDAL_REQUIRE(c > 0 && c <= kMaxClasses, "interframe_score: classes must be in 1..%d", kMaxClasses);
   LIDAL_REQUIRE(n_nei >= 0 && n_nei <= MAXNEI, "interframe_score: at most %d neighbours", MAXNEI);
   if (p == 0) return 0;
   LIDAL_REQUIRE(ws_bytes >= lidal_interframe_workspace_bytes(p, n_nei), "interframe workspace too small");
@@ -525,7 +505,7 @@ extern "C" int lidal_register_points(const float* points, int64_t p, const doubl
 extern "C" int lidal_confusion_accumulate(const float* logits, const int64_t* inverse,
                                           const int64_t* labels, int64_t p, int c, int32_t* conf,
                                           void* stream) {
-  LIDAL_REQUIRE(c > 0 && c <= MAXC, "confusion: classes must be in 1..%d", MAXC);
+  LIDAL_REQUIRE(c > 0 && c <= kMaxClasses, "confusion: classes must be in 1..%d", kMaxClasses);
   if (p == 0) return 0;
   confusion_kernel<<<(unsigned)cdiv(p, 256), 256, 0, (hipStream_t)stream>>>(logits, inverse, labels,
                                                                             p, c, conf);

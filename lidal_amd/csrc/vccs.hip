@@ -15,16 +15,18 @@
 #include <math.h>
 
 #include "common.h"
+#include "grid.h"
+#include "sym3.h"
 
 using namespace lidal;
+using namespace lidal::grid;
+using namespace lidal::sym3;
 
 namespace {
 
 constexpr int VC_BLOCK = 256;
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_TILE = VC_BLOCK * SCAN_ITEMS;       // flags per block of the scan
-constexpr int CELL_BITS = 21;                          // per axis; the cell + 2^20 is in [0, 2^21)
-constexpr int64_t CELL_BIAS = 1ll << 20;
 constexpr int LABEL_BITS = 24;                         // a label is at most the frame's voxels, below 2^24
 // status words (include/lidal_amd.h)
 constexpr int ST_ERR = 0, ST_V = 1, ST_G = 2, ST_S = 3, ST_PTR = 4;
@@ -32,19 +34,6 @@ constexpr int ST_ERR = 0, ST_V = 1, ST_G = 2, ST_S = 3, ST_PTR = 4;
 typedef unsigned long long u64;
 
 __device__ __forceinline__ void raise(long long* status, int word) { atomicMax((u64*)&status[ST_ERR], (u64)word); }
-
-__device__ __forceinline__ bool pack_cell(int64_t x, int64_t y, int64_t z, u64* key) {
-  const int64_t bx = x + CELL_BIAS, by = y + CELL_BIAS, bz = z + CELL_BIAS, lim = 1ll << CELL_BITS;
-  if (bx < 0 || bx >= lim || by < 0 || by >= lim || bz < 0 || bz >= lim) return false;
-  *key = ((u64)bx << (2 * CELL_BITS)) | ((u64)by << CELL_BITS) | (u64)bz;
-  return true;
-}
-__device__ __forceinline__ void unpack_cell(u64 key, int64_t* x, int64_t* y, int64_t* z) {
-  const u64 m = (1ull << CELL_BITS) - 1;
-  *x = (int64_t)(key >> (2 * CELL_BITS)) - CELL_BIAS;
-  *y = (int64_t)((key >> CELL_BITS) & m) - CELL_BIAS;
-  *z = (int64_t)(key & m) - CELL_BIAS;
-}
 
 // position of `key` among the ascending keys[lo, hi), or -1: at most 32 halvings
 __device__ __forceinline__ int find_key(const u64* __restrict__ keys, int lo, int hi, u64 key) {
@@ -142,8 +131,8 @@ __global__ void __launch_bounds__(VC_BLOCK) point_key_kernel(const float* __rest
   pframe[i] = lo;
   iota[i] = (int)i;
   const double x = (double)xyz[i * 3 + 0], y = (double)xyz[i * 3 + 1], z = (double)xyz[i * 3 + 2];
-  u64 k = 0;
-  if (!pack_cell((int64_t)floor(x / rv), (int64_t)floor(y / rv), (int64_t)floor(z / rv), &k)) raise(status, LIDAL_VCCS_CELL_RANGE);
+  uint64_t k = 0;
+  if (!cell_pack((int64_t)floor(x / rv), (int64_t)floor(y / rv), (int64_t)floor(z / rv), &k)) raise(status, LIDAL_VCCS_CELL_RANGE);
   key[i] = k;
 }
 
@@ -207,7 +196,7 @@ __global__ void __launch_bounds__(VC_BLOCK) centroid_kernel(int64_t cap, const l
   const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= cap || v >= status[ST_V]) return;
   int64_t c[3];
-  unpack_cell(vkey[v], &c[0], &c[1], &c[2]);
+  cell_unpack(vkey[v], &c[0], &c[1], &c[2]);
   const double n = (double)nv[v];
   for (int a = 0; a < 3; ++a) {
     cells[v * 3 + a] = (int)c[a];
@@ -225,11 +214,11 @@ __global__ void __launch_bounds__(VC_BLOCK) adjacency_kernel(int64_t cap, long l
   const int o = (int)(t / cap);
   if (o >= 27 || v >= status[ST_V]) return;
   int64_t x, y, z;
-  unpack_cell(vkey[v], &x, &y, &z);
+  cell_unpack(vkey[v], &x, &y, &z);
   const int f = vframe[v];
-  u64 k;
+  uint64_t k;
   int u = -1;
-  if (pack_cell(x + o / 9 - 1, y + (o / 3) % 3 - 1, z + o % 3 - 1, &k))
+  if (cell_pack(x + o / 9 - 1, y + (o / 3) % 3 - 1, z + o % 3 - 1, &k))
     u = find_key(vkey, (int)status[ST_PTR + f], (int)status[ST_PTR + f + 1], k);
   if (o == 13 && u != (int)v) raise(status, LIDAL_VCCS_NO_SLOT);
   nbr[(int64_t)o * cap + v] = u;
@@ -237,8 +226,8 @@ __global__ void __launch_bounds__(VC_BLOCK) adjacency_kernel(int64_t cap, long l
 
 // ---------------------------------------------------------------- normals
 // One thread per voxel.  S(v): the voxels within two adjacency steps, as a 125-bit mask over the cell offsets
-// (dx + 2) * 25 + (dy + 2) * 5 + (dz + 2), walked in ascending order; mean, population covariance and cyclic Jacobi as
-// knn_sigma (redal.hip) has them, the rotations applied to an eigenvector matrix as well.
+// (dx + 2) * 25 + (dy + 2) * 5 + (dz + 2), walked in ascending order; mean, population covariance and cyclic Jacobi are
+// sym3.h's, the ones of the surface variation (redal.hip), the rotations applied to an eigenvector matrix as well.
 __global__ void __launch_bounds__(VC_BLOCK) normal_kernel(int64_t cap, long long* status, const u64* __restrict__ vkey,
                                                           const int* __restrict__ vframe, const int* __restrict__ nbr,
                                                           const double* __restrict__ cen, double* __restrict__ nrm,
@@ -260,62 +249,25 @@ __global__ void __launch_bounds__(VC_BLOCK) normal_kernel(int64_t cap, long long
   double n3[3] = {0.0, 0.0, 0.0};
   if (count >= 3) {
     int64_t x, y, z;
-    unpack_cell(vkey[v], &x, &y, &z);
+    cell_unpack(vkey[v], &x, &y, &z);
     const int f = vframe[v];
     const int lo = (int)status[ST_PTR + f], hi = (int)status[ST_PTR + f + 1];
     auto member = [&](int idx) {
-      u64 k = 0;
+      uint64_t k = 0;
       int w = -1;
-      if (pack_cell(x + idx / 25 - 2, y + (idx / 5) % 5 - 2, z + idx % 5 - 2, &k)) w = find_key(vkey, lo, hi, k);
+      if (cell_pack(x + idx / 25 - 2, y + (idx / 5) % 5 - 2, z + idx % 5 - 2, &k)) w = find_key(vkey, lo, hi, k);
       if (w < 0) { raise(status, LIDAL_VCCS_NO_SLOT); w = (int)v; }
       return (int64_t)w;
     };
-    double mx = 0.0, my = 0.0, mz = 0.0;
-    for (int idx = 0; idx < 125; ++idx) {
-      if (!(((idx < 64 ? m0 >> idx : m1 >> (idx - 64))) & 1ull)) continue;
-      const int64_t w = member(idx);
-      mx += cen[w * 3 + 0]; my += cen[w * 3 + 1]; mz += cen[w * 3 + 2];
-    }
-    const double inv = 1.0 / (double)count;
-    mx *= inv; my *= inv; mz *= inv;
-    double a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0;
-    for (int idx = 0; idx < 125; ++idx) {
-      if (!(((idx < 64 ? m0 >> idx : m1 >> (idx - 64))) & 1ull)) continue;
-      const int64_t w = member(idx);
-      const double dx = cen[w * 3 + 0] - mx, dy = cen[w * 3 + 1] - my, dz = cen[w * 3 + 2] - mz;
-      a00 += dx * dx; a01 += dx * dy; a02 += dx * dz;
-      a11 += dy * dy; a12 += dy * dz; a22 += dz * dz;
-    }
-    double a[3][3] = {{a00 * inv, a01 * inv, a02 * inv}, {a01 * inv, a11 * inv, a12 * inv}, {a02 * inv, a12 * inv, a22 * inv}};
-    double e[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-    auto rot = [&](int P, int Q) {
-      const double apq = a[P][Q];
-      if (apq == 0.0) return;
-      const double theta = (a[Q][Q] - a[P][P]) / (2.0 * apq);
-      const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-      const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-      const int r = 3 - P - Q;
-      const double arp = a[r][P], arq = a[r][Q];
-      a[r][P] = a[P][r] = c * arp - s * arq;
-      a[r][Q] = a[Q][r] = s * arp + c * arq;
-      a[P][P] -= t * apq;
-      a[Q][Q] += t * apq;
-      a[P][Q] = a[Q][P] = 0.0;
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const double ep = e[i][P], eq = e[i][Q];
-        e[i][P] = c * ep - s * eq;
-        e[i][Q] = s * ep + c * eq;
+    double a[3][3], e[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    covariance3([&](auto visit) {
+      for (int idx = 0; idx < 125; ++idx) {
+        if (!(((idx < 64 ? m0 >> idx : m1 >> (idx - 64))) & 1ull)) continue;
+        const int64_t w = member(idx);
+        visit(cen[w * 3 + 0], cen[w * 3 + 1], cen[w * 3 + 2]);
       }
-    };
-    for (int sweep = 0; sweep < 32; ++sweep) {
-      const double off = fabs(a[0][1]) + fabs(a[0][2]) + fabs(a[1][2]);
-      const double dia = fabs(a[0][0]) + fabs(a[1][1]) + fabs(a[2][2]);
-      if (!(off > 1e-300) || off <= 1e-18 * dia) break;
-      rot(0, 1);
-      rot(0, 2);
-      rot(1, 2);
-    }
+    }, count, a);
+    jacobi3<true>(a, e);
     // the column of the smallest diagonal entry, the lowest index among equals
     double best = a[0][0];
     n3[0] = e[0][0]; n3[1] = e[1][0]; n3[2] = e[2][0];
@@ -348,8 +300,8 @@ __global__ void __launch_bounds__(VC_BLOCK) seed_key_kernel(int64_t cap, long lo
     c[a] = (int64_t)floor(x / rs);
     d[a] = x - ((double)c[a] + 0.5) * rs;
   }
-  u64 k = 0;
-  if (!pack_cell(c[0], c[1], c[2], &k)) raise(status, LIDAL_VCCS_CELL_RANGE);
+  uint64_t k = 0;
+  if (!cell_pack(c[0], c[1], c[2], &k)) raise(status, LIDAL_VCCS_CELL_RANGE);
   key[v] = k;
   sd2[v] = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
 }
@@ -590,7 +542,7 @@ VccsWs vccs_layout(int64_t p_total, int n_frames, void* ws) {
 // batch, by the frame.  Returns the array that holds the sorted items.
 int sort_by_frame_key(const VccsWs& w, const int* frame_of, int64_t cap, int n_frames, int fbits, const long long* n_live,
                       const int** sorted, hipStream_t s) {
-  if (int rc = radix_sort(w.key, w.idx_a, w.skey, w.idx_b, cap, 8, 3 * CELL_BITS, w.sort, w.sort_bytes, s,
+  if (int rc = radix_sort(w.key, w.idx_a, w.skey, w.idx_b, cap, 8, 3 * kCellBits, w.sort, w.sort_bytes, s,
                           (const int64_t*)n_live))
     return rc;
   *sorted = w.idx_b;

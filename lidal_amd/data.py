@@ -342,6 +342,32 @@ def _finite_points(xyz, what):
                          % (what, reach, SV_REACH))
 
 
+def _batch(frames):                        # laid end to end: (all rows, ptr host i64 [n + 1], where each frame starts)
+    ptr = np.concatenate([[0], np.cumsum([x.shape[0] for x in frames])]).astype(np.int64)
+    return (frames[0] if len(frames) == 1 else torch.cat(frames)), ptr
+
+
+def _scan_batch(points, what, check):
+    """One scan [P, 3] or a list of scans -> (frames f32 contiguous, xyz f32 [sum P, 3], ptr host i64 [n + 1], single).
+    Refused before require_gpu and before any launch: no scans, a scan that is not [P, 3], what check(frames) raises."""
+    single = torch.is_tensor(points)
+    frames = [points] if single else list(points)
+    if not frames:
+        raise ValueError('%s: no scans' % what)
+    for x in frames:
+        if not torch.is_tensor(x) or x.ndim != 2 or x.shape[1] != 3:
+            raise ValueError('%s: points must be [P, 3], not %s' % (what, tuple(getattr(x, 'shape', ())),))
+    check(frames)
+    B.require_gpu(*frames)
+    frames = [x.float().contiguous() for x in frames]
+    xyz, ptr = _batch(frames)
+    return frames, xyz, ptr, single
+
+
+def _sv_ptr(sizes, dev):                   # a frame's supervoxel sizes (host) -> sv_ptr i64 [S + 1] on the device
+    return torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)).to(dev)
+
+
 def supervoxel_costs(xyz, centers):
     """The integer arc costs of the definition: xyz f32 [P,3] and centers f64 [K,3] on the GPU -> int32 [P,K],
     rint(1000 * distance) with the distance in f64 as numpy rounds it."""
@@ -380,9 +406,8 @@ def balanced_assign(cost, size_min, size_max):
         _check_bounds(c.shape[0], k, l, h, 'balanced_assign')
     B.require_gpu(*frames)
     dev = frames[0].device
-    ptr = np.concatenate([[0], np.cumsum([c.shape[0] for c in frames])]).astype(np.int64)
+    cost_all, ptr = _batch([c.contiguous() for c in frames])
     p_total = int(ptr[-1])
-    cost_all = frames[0].contiguous() if n == 1 else torch.cat([c.contiguous() for c in frames])
     ptr_dev = torch.from_numpy(ptr).to(dev)
     lo_dev = torch.tensor(lo, dtype=torch.int32, device=dev)
     hi_dev = torch.tensor(hi, dtype=torch.int32, device=dev)
@@ -414,31 +439,23 @@ def kmeans_supervoxels(points, n_clusters=20, slack=0.05, random_state=0, detail
     Raises ValueError, before any launch, for n_clusters outside 1..64, fewer points than clusters, size bounds no
     assignment can meet (21 points in 20 clusters: size_max is 1) and coordinates that are not finite."""
     from .score.redal import kmeans_draws
-    single = torch.is_tensor(points)
-    frames = [points] if single else list(points)
-    if not frames:
-        raise ValueError('kmeans_supervoxels: no scans')
     k = int(n_clusters)
     lo, hi = [], []
-    for x in frames:
-        if x.ndim != 2 or x.shape[1] != 3:
-            raise ValueError('kmeans_supervoxels: points must be [P, 3], not %s' % (tuple(x.shape),))
-        l, h = supervoxel_bounds(x.shape[0], k, slack) if 1 <= k <= SV_KMAX else (0, 0)
-        _check_bounds(x.shape[0], k, l, h, 'kmeans_supervoxels')
-        lo.append(l), hi.append(h)
-    B.require_gpu(*frames)
-    frames = [x.float().contiguous() for x in frames]
-    xyz = frames[0] if len(frames) == 1 else torch.cat(frames)
+
+    def check(frames):
+        for x in frames:
+            l, h = supervoxel_bounds(x.shape[0], k, slack) if 1 <= k <= SV_KMAX else (0, 0)
+            _check_bounds(x.shape[0], k, l, h, 'kmeans_supervoxels')
+            lo.append(l), hi.append(h)
+    frames, xyz, ptr, single = _scan_batch(points, 'kmeans_supervoxels', check)
     _finite_points(xyz, 'kmeans_supervoxels')
-    n = len(frames)
-    dev = xyz.device
+    n, dev = len(frames), xyz.device
     seed = int(np.random.RandomState(random_state).randint(2 ** 31 - 1, size=1)[0])
     draws = [kmeans_draws(x.shape[0], k, seed) for x in frames]
     trials = draws[0][2]
     first = np.array([d[0] for d in draws], dtype=np.int64)
     u = np.concatenate([d[1].reshape(-1) for d in draws] + [np.zeros(1)])
     u_dev = torch.from_numpy(u).to(dev)
-    ptr = np.concatenate([[0], np.cumsum([x.shape[0] for x in frames])]).astype(np.int64)
     p_total, p_max = int(ptr[-1]), int(max(x.shape[0] for x in frames))
     lo_h, hi_h = np.array(lo, dtype=np.int32), np.array(hi, dtype=np.int32)
     seeds = torch.empty((n, k), dtype=torch.int32, device=dev)
@@ -463,9 +480,7 @@ def kmeans_supervoxels(points, n_clusters=20, slack=0.05, random_state=0, detail
     out = []
     for f in range(n):
         a, b = int(ptr[f]), int(ptr[f + 1])
-        sizes = counts_h[f][counts_h[f] > 0].astype(np.int64)
-        sv_ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)).to(dev)
-        item = (labels[a:b].long(), sv_ptr, order[a:b].long())
+        item = (labels[a:b].long(), _sv_ptr(counts_h[f][counts_h[f] > 0], dev), order[a:b].long())
         if details:
             item += (dict(seeds=seeds[f], labels_first=labels_first[a:b].long(), centers=centers[f], counts=counts[f],
                           objective=(int(objective_h[0, f]), int(objective_h[1, f])),
@@ -488,8 +503,6 @@ def vccs_parameters(voxel_resolution=0.5, seed_resolution=10.0):
 
 
 def _check_vccs(frames, rv, rs, w_s, w_n):
-    if not frames:
-        raise ValueError('vccs_supervoxels: no scans')
     if not (rv > 0 and math.isfinite(rv) and math.isfinite(rs)):
         raise ValueError('vccs_supervoxels: voxel_resolution=%r must be positive and finite' % rv)
     if rs < 2 * rv:
@@ -499,8 +512,6 @@ def _check_vccs(frames, rv, rs, w_s, w_n):
     if not (w_s >= 0 and w_n >= 0 and math.isfinite(w_s) and math.isfinite(w_n)):
         raise ValueError('vccs_supervoxels: the importances must not be negative')
     for x in frames:
-        if not torch.is_tensor(x) or x.ndim != 2 or x.shape[1] != 3:
-            raise ValueError('vccs_supervoxels: points must be [P, 3], not %s' % (tuple(getattr(x, 'shape', ())),))
         if x.shape[0] == 0:
             raise ValueError('vccs_supervoxels: a scan without points')
         if x.shape[0] >= 2 ** 24:
@@ -508,6 +519,8 @@ def _check_vccs(frames, rv, rs, w_s, w_n):
     if sum(x.shape[0] for x in frames) >= 2 ** 31 // 27:
         raise ValueError('vccs_supervoxels: %d points in one batch (fewer than %d)'
                          % (sum(x.shape[0] for x in frames), 2 ** 31 // 27))
+    for x in frames:
+        _finite_points(x, 'vccs_supervoxels')
 
 
 def vccs_supervoxels(points, voxel_resolution=0.5, seed_resolution=10.0, spatial_importance=0.4, normal_importance=1.0,
@@ -522,19 +535,11 @@ def vccs_supervoxels(points, voxel_resolution=0.5, seed_resolution=10.0, spatial
     (prepare_supervoxel_VCCS_sk.py:72-77), in the form score_frame, region_scores, segment_entropy and train_labels
     take.  details=True appends a dict with cells, centroids, normals, point_voxel, qs, n, seed_voxels, owners, counts,
     rounds, min_seed.  Raises ValueError before any launch for what the definition refuses."""
-    single = torch.is_tensor(points)
-    frames = [points] if single else list(points)
     rv, rs = float(voxel_resolution), float(seed_resolution)
     w_s, w_n = float(spatial_importance), float(normal_importance)
-    _check_vccs(frames, rv, rs, w_s, w_n)
-    for x in frames:
-        _finite_points(x, 'vccs_supervoxels')
-    B.require_gpu(*frames)
-    frames = [x.float().contiguous() for x in frames]
-    xyz = frames[0] if len(frames) == 1 else torch.cat(frames)
+    frames, xyz, ptr, single = _scan_batch(points, 'vccs_supervoxels', lambda fr: _check_vccs(fr, rv, rs, w_s, w_n))
     min_seed, rounds = vccs_parameters(rv, rs)
     n, dev = len(frames), xyz.device
-    ptr = np.concatenate([[0], np.cumsum([x.shape[0] for x in frames])]).astype(np.int64)
     p = int(ptr[-1])
     i32 = dict(dtype=torch.int32, device=dev)
     labels = torch.empty(p, dtype=torch.int64, device=dev)
@@ -565,8 +570,7 @@ def vccs_supervoxels(points, voxel_resolution=0.5, seed_resolution=10.0, spatial
         local = order[a:b].long() - a                          # the scan's points by (label, point); label 0 first
         parts = [local[int(t):int(t) + int(c)] for t, c in zip(starts[keep], sizes[keep])]
         sv_idx = torch.cat(parts) if parts else torch.empty(0, dtype=torch.int64, device=dev)
-        sv_ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes[keep])]).astype(np.int64)).to(dev)
-        item = (labels[a:b], sv_ptr, sv_idx)
+        item = (labels[a:b], _sv_ptr(sizes[keep], dev), sv_idx)
         if details:
             item += (dict(cells=cells[v0:v1], centroids=cen[v0:v1], normals=nrm[v0:v1], qs=qs[v0:v1], n=nv[v0:v1],
                           point_voxel=point_voxel[a:b].long() - v0, seed_voxels=seed_voxels[s0:s1].long() - v0,

@@ -1,7 +1,9 @@
-"""numpy restatement of the project's k-means definition (csrc/redal.hip), of worker_func's
+"""numpy restatement of the project's k-means definition (csrc/kmeans.hip), of worker_func's
 per-region reductions and of the k-nearest-neighbour list and surface variation: test infrastructure, the CPU side of
 the bit-for-bit checks."""
 import numpy as np
+
+from jacobi_ref import jacobi3
 
 CHUNK = 256
 NP_BUFSIZE = 8192       # numpy's ufunc buffer size: an add-reduce sees blocks of at most this many values
@@ -224,6 +226,37 @@ def surface_variation_f64(xyz, nb):
     cov = np.einsum('pki,pkj->pij', e, e) / nb.shape[1]
     lam = np.linalg.eigvalsh(cov)
     return lam[:, 0] / lam.sum(axis=1)
+
+
+def surface_variation_jacobi(xyz, nb, threshold=0.1):
+    """The surface variation as knn_kernel computes it, bit for bit: the mean and the population covariance of each
+    point's neighbours nb [P,k] summed in neighbour order (f64, every product and sum rounded), the eigenvalues by the
+    shared cyclic Jacobi (tests/jacobi_ref.py), f32(min / (l0 + l1 + l2)), then the kernel's clip: a value above
+    f32(threshold) becomes it, NaN (a neighbourhood of one repeated point: 0 / 0) passes.  f32 [P]."""
+    x = np.asarray(xyz, dtype=np.float32).astype(np.float64)
+    k = nb.shape[1]
+    inv = 1.0 / float(k)
+    thr = np.float32(np.inf if threshold is None else threshold)
+    out = np.empty(len(nb), np.float32)
+    for i, row in enumerate(nb):
+        pts = [[float(v) for v in x[j]] for j in row]
+        m = [0.0, 0.0, 0.0]
+        for q in pts:
+            m = [m[0] + q[0], m[1] + q[1], m[2] + q[2]]
+        m = [m[0] * inv, m[1] * inv, m[2] * inv]
+        a00 = a01 = a02 = a11 = a12 = a22 = 0.0
+        for q in pts:
+            dx, dy, dz = q[0] - m[0], q[1] - m[1], q[2] - m[2]
+            a00 += dx * dx; a01 += dx * dy; a02 += dx * dz
+            a11 += dy * dy; a12 += dy * dz; a22 += dz * dz
+        a = [[a00 * inv, a01 * inv, a02 * inv], [a01 * inv, a11 * inv, a12 * inv], [a02 * inv, a12 * inv, a22 * inv]]
+        jacobi3(a)
+        l0, l1, l2 = a[0][0], a[1][1], a[2][2]
+        lmin = min(l0, l1, l2)                                      # (finite inputs: no NaN reaches the fmin)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            sigma = np.float32(np.float64(lmin) / np.float64(l0 + l1 + l2))
+        out[i] = thr if sigma > thr else sigma
+    return out
 
 
 def same_partition(a, b):

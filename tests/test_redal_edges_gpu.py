@@ -281,6 +281,40 @@ def test_surface_variation_degenerate_neighbourhoods():
         assert np.isnan(s[copies]).all() and not np.isnan(s[~copies]).any()
 
 
+def _jacobi_cases():
+    """(name, xyz, k): the least k on k + 1 points, one full workgroup's worth short of one, a second, partial 64-lane
+    workgroup, distance ties, and neighbours that all coincide (0 / 0)."""
+    rs = np.random.RandomState(53)
+    g = np.arange(3.0)
+    return [('k3_on_4', rs.normal(0, 1, size=(4, 3)), 3), ('k8_on_9', rs.normal(0, 1, size=(9, 3)), 8),
+            ('70_random', rs.normal(0, 2, size=(70, 3)) * [3.0, 1.0, 0.2], 8),
+            ('lattice_3x3x3', np.stack(np.meshgrid(g, g, g, indexing='ij'), -1).reshape(-1, 3) * 0.25, 8),
+            ('5_coincident', np.repeat([[1.5, -2.0, 0.25]], 5, axis=0), 4)]
+
+
+@pytest.mark.parametrize('case', _jacobi_cases(), ids=lambda c: c[0])
+def test_surface_variation_equals_the_jacobi_restatement_bit_for_bit(case):
+    """The sweep that redal.hip and vccs.hip share (csrc/sym3.h), pinned on this side too: sigma equals, bit for bit,
+    the restatement that sums mean and covariance in neighbour order and runs the numpy Jacobi the VCCS normals are
+    checked with (tests/jacobi_ref.py), unclipped and clipped at 0.1.  NaN compares as NaN.  (On these inputs the
+    restatement agrees with LAPACK's f64 eigenvalues, redal_ref.surface_variation_f64, to 5.3e-9, the f32 rounding of
+    its result: far inside the 1e-6 of test_surface_variation_random_clouds_against_f64_eigenvalues.)"""
+    from lidal_amd.score import knn
+    name, xyz, k = case
+    xyz = xyz.astype(np.float32)
+    nb = knn(_t(xyz), k).cpu().numpy()
+    assert np.array_equal(nb, redal_ref.knn_brute(xyz, k))
+    for thr in (None, 0.1):
+        got = _sigma(xyz, k=k, threshold=thr)
+        want = redal_ref.surface_variation_jacobi(xyz, nb, threshold=thr)
+        nan = np.isnan(want)
+        print('%s, threshold %s: %d values, %d NaN, %d differ' % (name, thr, len(want), nan.sum(),
+                                                                 (_bits(got)[~nan] != _bits(want)[~nan]).sum()))
+        assert np.array_equal(np.isnan(got), nan)
+        assert np.array_equal(_bits(got)[~nan], _bits(want)[~nan])
+    assert nan.all() == (name == '5_coincident')
+
+
 # ------------------------------------------------------------------------------------------------ k-means
 def _km_data(n, d, seed):
     """Normal rows, the last third copies of rows of the first third: clusters seeded on a repeated row are empty."""

@@ -11,11 +11,10 @@ import torch
 
 import vccs_inputs as VI
 import vccs_ref as R
+from guarded_ws import Guarded
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-GUARD = 4096
-FILL = 0xA5
 
 
 @pytest.fixture(scope='module')
@@ -149,26 +148,6 @@ def test_csr_is_the_reference_lists_and_feeds_scoring_and_training(name):
         scores, feats, pnums = redal.region_scores(_dev(prob), _dev(rng.random((p, 8)).astype(np.float32)),
                                                    _dev(rng.random(p).astype(np.float32)), sv_ptr, sv_idx)
         assert np.array_equal(pnums.cpu().numpy(), np.diff(want_ptr)) and bool(torch.isfinite(scores).all())
-
-
-class Guarded:
-    """Stand-in for backend.workspace: [guard | nbytes | guard], all 0xA5 (as tests/test_workspace_exact_gpu.py)."""
-
-    def __init__(self):
-        self.bufs = []
-
-    def __call__(self, nbytes, device=DEV):
-        nbytes = int(nbytes)
-        t = torch.full((GUARD + nbytes + GUARD,), FILL, dtype=torch.uint8, device=device)
-        self.bufs.append((t, nbytes))
-        return t[GUARD:GUARD + nbytes]
-
-    def check(self):
-        torch.cuda.synchronize()
-        assert self.bufs, 'the builder never asked for scratch'
-        for t, n in self.bufs:
-            assert bool((t[:GUARD] == FILL).all()), 'the guard below %d bytes of scratch was written' % n
-            assert bool((t[GUARD + n:] == FILL).all()), 'the guard above %d bytes of scratch was written' % n
 
 
 @pytest.mark.parametrize('names', [('one_point',), ('three_collinear',), ('ground_wall',), VI.BATCH])

@@ -27,11 +27,10 @@ import torch
 import frame_inputs as FI
 import geometry_ref as G
 import interframe_ref as IR
+from guarded_ws import Guarded
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-GUARD = 4096
-FILL = 0xA5
 SIZES = [1, 33, 65, 1024, 1025]
 K27, K8 = ((3, 3, 3), 1), ((2, 2, 2), 2)          # 27 offsets, symmetric; 8 offsets, strided
 
@@ -44,26 +43,6 @@ def _B():
 def _g(a, dtype=None):
     t = torch.from_numpy(np.ascontiguousarray(a))
     return (t if dtype is None else t.to(dtype)).to(DEV)
-
-
-class Guarded:
-    """Stand-in for backend.workspace: [guard | nbytes | guard], all 0xA5; every buffer is kept until the test ends."""
-
-    def __init__(self):
-        self.bufs = []
-
-    def __call__(self, nbytes, device=DEV):
-        nbytes = int(nbytes)
-        t = torch.full((GUARD + nbytes + GUARD,), FILL, dtype=torch.uint8, device=device)
-        self.bufs.append((t, nbytes))
-        return t[GUARD:GUARD + nbytes]
-
-    def check(self):
-        torch.cuda.synchronize()
-        assert self.bufs, 'the builder never asked for scratch'
-        for t, n in self.bufs:
-            assert bool((t[:GUARD] == FILL).all()), 'the guard below %d bytes of scratch was written' % n
-            assert bool((t[GUARD + n:] == FILL).all()), 'the guard above %d bytes of scratch was written' % n
 
 
 def _flat(x):

@@ -18,6 +18,8 @@ import math
 
 import numpy as np
 
+from jacobi_ref import jacobi3
+
 BIAS = 1 << 20
 OFF27 = np.array([(o // 9 - 1, (o // 3) % 3 - 1, o % 3 - 1) for o in range(27)], dtype=np.int64)
 
@@ -80,37 +82,8 @@ def two_ring(nbr):
 
 
 def _jacobi_normal(a, c):
-    """a: 3x3 list (symmetric), c: the voxel's centroid.  The cyclic Jacobi of redal.hip with eigenvectors."""
-    e = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]
-
-    def rot(p, q):
-        apq = a[p][q]
-        if apq == 0.0:
-            return
-        theta = (a[q][q] - a[p][p]) / (2.0 * apq)
-        t = (1.0 if theta >= 0.0 else -1.0) / (abs(theta) + math.sqrt(theta * theta + 1.0))
-        cs = 1.0 / math.sqrt(t * t + 1.0)
-        s = t * cs
-        r = 3 - p - q
-        arp, arq = a[r][p], a[r][q]
-        a[r][p] = a[p][r] = cs * arp - s * arq
-        a[r][q] = a[q][r] = s * arp + cs * arq
-        a[p][p] -= t * apq
-        a[q][q] += t * apq
-        a[p][q] = a[q][p] = 0.0
-        for i in range(3):
-            ep, eq = e[i][p], e[i][q]
-            e[i][p] = cs * ep - s * eq
-            e[i][q] = s * ep + cs * eq
-
-    for _ in range(32):
-        off = abs(a[0][1]) + abs(a[0][2]) + abs(a[1][2])
-        dia = abs(a[0][0]) + abs(a[1][1]) + abs(a[2][2])
-        if not (off > 1e-300) or off <= 1e-18 * dia:
-            break
-        rot(0, 1)
-        rot(0, 2)
-        rot(1, 2)
+    """a: 3x3 list (symmetric), c: the voxel's centroid.  The cyclic Jacobi of sym3.h (tests/jacobi_ref.py)."""
+    e = jacobi3(a)
     m = 0
     if a[1][1] < a[m][m]:
         m = 1
