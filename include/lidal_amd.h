@@ -592,6 +592,26 @@ int lidal_supervoxel_reduce(const double* interd, const float* intere, const dou
                             const int64_t* sv_ptr, const int64_t* sv_idx, int s, float* sv_interd,
                             float* sv_intere, float* sv_center, void* stream);
 
+/* ---- fixed-radius neighbour lists of the supervoxel centres (csrc/neighbours.hip) ---------- */
+/* The distance work of score/sv_level/LiDAL.py:225-325 (the greedy selection tests a candidate against every added
+ * supervoxel): the CSR table of all pairs within `radius`, centers f32 [n,3].  Row i = every j != i, ascending, with
+ *     sqrt(((dx*dx + dy*dy) + dz*dz)) < radius        in f32, every operation rounded, the root correctly rounded,
+ * the reference's `np.sqrt(np.square(c_i - c_j).sum()) < radius` bit for bit; symmetric; a function of the centres alone.
+ * Two calls make one table: lidal_radius_pairs_count writes row_ptr i64 [n + 1] (device), the caller reads row_ptr[n],
+ * allocates col i32 [row_ptr[n]] and calls lidal_radius_pairs_fill with the same centres, radius and row_ptr (the fill
+ * does not depend on what the workspace held in between).  A centre with a NaN or infinite coordinate has an empty row
+ * and is in no row.  A finite coordinate whose cell index (cell = the smallest power of two >= radius) does not fit 21
+ * bits raises *status_dev (i32 [1], written by every count call; the table is then not valid).  n <= 2^31 - 1; n = 0, 1:
+ * empty tables; radius finite, >= 2^-60.  Workspace: lidal_radius_pairs_workspace_bytes(n), for both calls. */
+enum {
+  LIDAL_PAIRS_CELL_RANGE = 1   /* a finite centre outside the 21 bits per axis of the cell key */
+};
+int64_t lidal_radius_pairs_workspace_bytes(int64_t n);
+int lidal_radius_pairs_count(const float* centers, int64_t n, float radius, int64_t* row_ptr, int32_t* status_dev,
+                             void* ws, int64_t ws_bytes, void* stream);
+int lidal_radius_pairs_fill(const float* centers, int64_t n, float radius, const int64_t* row_ptr, int32_t* col,
+                            void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- ReDAL region selection (score/sv_level/ReDAL.py, dataset/ReDAL/gen_surface_variation_sk.py; csrc/redal.hip) ---- */
 /* k nearest OTHER points of every point of a raw scan xyz f32 [p,3]: knn i32 [p,k], sorted by (f64 distance, index).
  * 1 <= k <= 64; p < k + 1 is refused (status 2, lidal_last_error).  `cell`: the search grid's cell in metres (the

@@ -140,6 +140,9 @@ SIGNATURES = {
     'lidal_interframe_score_ordered': (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _f64, _vp,
                                               _vp, _vp, _vp, _i64, _vp, _vp]),
     'lidal_supervoxel_reduce': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    'lidal_radius_pairs_workspace_bytes': (_i64, [_i64]),
+    'lidal_radius_pairs_count': (_i32, [_vp, _i64, _f32, _vp, _vp, _vp, _i64, _vp]),
+    'lidal_radius_pairs_fill': (_i32, [_vp, _i64, _f32, _vp, _vp, _vp, _i64, _vp]),
     'lidal_knn_workspace_bytes': (_i64, [_i64]),
     'lidal_knn': (_i32, [_vp, _i64, _i32, _f64, _vp, _vp, _i64, _vp]),
     'lidal_surface_variation': (_i32, [_vp, _i64, _i32, _f64, _f32, _vp, _vp, _i64, _vp]),

@@ -10,10 +10,11 @@ from .pipeline import ScoreBoard, collect_sequence, score_sequence
 from .prob_inference import infer_frame
 from .redal import (RegionBoard, kmeans, knn, redal_sequence, region_scores, select_redal,
                     surface_variation)
-from .selection import select
+from .selection import centre_pairs, select, select_indexed
 from .sharding import HaloExchange, frame_range, gather_frames, needed_frames
 
 __all__ = ['infer_frame', 'FrameBank', 'neighbour_ids', 'score_frame', 'score_sequence', 'collect_sequence', 'ScoreBoard', 'select',
+           'select_indexed', 'centre_pairs',
            'frame_range', 'gather_frames', 'needed_frames', 'HaloExchange',
            'surface_variation', 'knn', 'region_scores', 'kmeans', 'select_redal', 'RegionBoard', 'redal_sequence',
            'frame_uncertainty', 'segment_entropy', 'frame_feature', 'coreset', 'select_frames', 'random_frames',

@@ -15,7 +15,7 @@ import torch.distributed as dist
 
 from .interframe import FrameBank, score_frame
 from .prob_inference import infer_frame
-from .selection import select
+from .selection import select, select_indexed
 from .sharding import HaloExchange, gather_frames, is_sharded
 
 __all__ = ['score_sequence', 'collect_sequence', 'ScoreBoard']
@@ -255,6 +255,11 @@ class ScoreBoard:
                 # offset that keeps supervoxels of different sequences > 5 m apart (:218)
                 self.sv_centers[sv_id] = c + seq_index * 1000.0
 
-    def select(self, sv_flags, train_point_num, sv_dis_thresh=5.0):
+    def select(self, sv_flags, train_point_num, sv_dis_thresh=5.0, indexed=False, pairs=None):
+        """indexed=True: the same flags from select_indexed, the distance work on the GPU (`pairs`: a table of
+        centre_pairs(self.sv_centers, sv_dis_thresh) made earlier, or None to make it now)."""
+        if indexed:
+            return select_indexed(sv_flags, self.sv_interds, self.sv_interes, self.sv_pnums, self.sv_centers,
+                                  train_point_num, sv_dis_thresh, pairs=pairs)
         return select(sv_flags, self.sv_interds, self.sv_interes, self.sv_pnums, self.sv_centers,
                       train_point_num, sv_dis_thresh)
