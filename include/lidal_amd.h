@@ -122,6 +122,27 @@ int lidal_voxelize_points(const float* points, const float* intensity, int64_t p
                           int64_t* n_out_dev, int32_t* n_invalid_dev, void* ws, int64_t ws_bytes,
                           void* stream);
 
+/* The same for a WHOLE BATCH and its collate_fn (dataset/sk_dataset.py:188-242) in one call: n_samples <= 32 samples --
+ * the scans of a training / validation batch, or the augmented views of ONE scan (dataset/sk_dataloader.py:199-203) --
+ * from ONE sort of sample << 39 | x << 26 | y << 13 | z over all points, with ONE small buffer to read back.  Every
+ * output equals, bit for bit, n_samples calls of lidal_voxelize_points collated as collate_fn does.
+ *   points f32 [*,3], intensity f32 [*] (device); src_row0 / n_points i64 [n_samples] (HOST): sample j reads the
+ *   source rows src_row0[j] .. src_row0[j] + n_points[j] (two samples may read the same rows) and owns the rows
+ *   point_ptr[j] .. point_ptr[j+1] of the batch's concatenated point list, point_ptr = the running sum of n_points;
+ *   p_total = point_ptr[n_samples] < 2^30.  m_dev f64 [n_samples,9], rnd_dev f64 [n_samples,6]: one matrix and one
+ *   set of draws per sample.
+ *   coords_v_b i32 [p_total,4] capacity (sample index in column 3), feats_v_b f32 [p_total,4] capacity (the feature
+ *   row of each voxel's first-occurrence point, gathered inside the call), unique_idx i64 [p_total] capacity (first
+ *   occurrence as a row of the concatenated point list), inverse_b i64 [p_total] (already offset by the voxels of the
+ *   samples before, as collate_fn offsets it), counts_dev: voxel_ptr i64 [n_samples+1] (sample j's voxels are the
+ *   rows voxel_ptr[j] .. voxel_ptr[j+1]) followed by n_invalid i32 [n_samples] (points outside the grid, per sample).
+ *   A sample without points contributes no rows and no error. */
+int64_t lidal_voxelize_batch_workspace_bytes(int64_t p_total, int n_samples);
+int lidal_voxelize_batch(const float* points, const float* intensity, const int64_t* src_row0,
+                         const int64_t* n_points, int n_samples, const double* m_dev, const double* rnd_dev,
+                         double scale, int full_scale, int32_t* coords_v_b, float* feats_v_b, int64_t* unique_idx,
+                         int64_t* inverse_b, int64_t* counts_dev, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- training labels from the round's flags (csrc/labels.hip) ------------------------------------ */
 /* replaces dataset/sk_dataset.py:106-141,170-171 (and dataset/nu_dataset.py:128-160,189-190) for one scan:
  *   raw         the bytes of the annotation file, u32 [p] (raw_bytes == 4, SemanticKITTI: `labels_anno_p & 0xFFFF`,

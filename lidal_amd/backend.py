@@ -47,6 +47,9 @@ SIGNATURES = {
     'lidal_voxelize_points_workspace_bytes': (_i64, [_i64]),
     'lidal_voxelize_points': (_i32, [_vp, _vp, _i64, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _i64, _vp]),
+    'lidal_voxelize_batch_workspace_bytes': (_i64, [_i64, _i32]),
+    'lidal_voxelize_batch': (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                    _vp]),
     'lidal_train_labels_workspace_bytes': (_i64, [_i64]),
     'lidal_train_labels': (_i32, [_vp, _i32, _i64, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                   _vp, _i64, _vp]),

@@ -1272,3 +1272,240 @@ extern "C" int lidal_voxelize_points(const float* points, const float* intensity
   LIDAL_CHECK_LAUNCH("rows_compact");
   return 0;
 }
+
+// ---- input voxelisation of a WHOLE BATCH in one go (sk_dataset.py:143-171 per sample + collate_fn :188-242) ----------
+// S samples (the scans of a training / validation batch, or S augmented views of ONE scan: two samples may read the same
+// source rows) laid end to end in ONE key array, key = sample << 39 | x << 26 | y << 13 | z, sorted once with the
+// concatenated point row as value.  The sort is stable, so after it: the heads of the runs, in order, are the rows of
+// collate_fn's coords_v_b (sample-major, lexicographic inside a sample: np.unique per sample, concatenated); the number of
+// a point's run is its collated inverse index (collate_fn adds the voxels of the samples before it: the runs before the
+// sample's first); the first point of a run is its first occurrence; the run number of a sample's first key is where its
+// voxels start.  Every kernel takes the sample descriptors by value (nothing to upload).  The per-point arithmetic is
+// that of affine_kernel / voxel_offset_kernel / voxel_keys_kernel operation for operation; the scaled coordinates are
+// recomputed from the 12-byte source row where the single form stores and re-reads 24 bytes, and the feature row of a
+// voxel is recomputed at its run head (same expressions, same rounding), so no per-point array leaves the call.
+namespace {
+constexpr int MAX_VOXELIZE_SAMPLES = 32;
+struct VoxelBatch {
+  long long src0[MAX_VOXELIZE_SAMPLES];          // first source row of sample j in points / intensity
+  long long row0[MAX_VOXELIZE_SAMPLES + 1];      // first row of sample j in the concatenated point list
+  long long block0[MAX_VOXELIZE_SAMPLES + 1];    // first 256-point block of sample j: no block straddles two samples
+  int n_samples;
+};
+
+// p * M for one source row (row vector times matrix, k = 0, 1, 2 in order, every product and sum rounded)
+__device__ __forceinline__ void affine_point(const float* __restrict__ pts, long long row, const double* __restrict__ M,
+                                             double v[3]) {
+  const double x = (double)pts[row * 3 + 0], y = (double)pts[row * 3 + 1], z = (double)pts[row * 3 + 2];
+#pragma unroll
+  for (int j = 0; j < 3; ++j)
+    v[j] = __dadd_rn(__dadd_rn(__dmul_rn(x, M[0 * 3 + j]), __dmul_rn(y, M[1 * 3 + j])), __dmul_rn(z, M[2 * 3 + j]));
+}
+
+// min of v[0..2] and max of v[3..5] over the 256 threads of the block, in red[.][0]
+__device__ __forceinline__ void block_minmax6(double v[6], double (*red)[4]) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      v[j] = fmin(v[j], __shfl_xor(v[j], off, 64));
+      v[3 + j] = fmax(v[3 + j], __shfl_xor(v[3 + j], off, 64));
+    }
+  if (lane_id() == 0) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) red[j][threadIdx.x >> 6] = v[j];
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    const int j = threadIdx.x;
+    double a = red[j][0];
+    for (int w = 1; w < 4; ++w) a = j < 3 ? fmin(a, red[j][w]) : fmax(a, red[j][w]);
+    red[j][0] = a;
+  }
+  __syncthreads();
+}
+
+// 1. per-block min / max of the scaled coordinates; a block belongs to ONE sample
+__global__ void __launch_bounds__(256) affine_batch_kernel(VoxelBatch b, const float* __restrict__ pts,
+                                                           const double* __restrict__ M /*[S,9]*/, double scale,
+                                                           double* __restrict__ part /*[blocks][6]*/) {
+  __shared__ double red[6][4];
+  const int j = job_of(b.block0, b.n_samples, blockIdx.x);
+  const long long r = ((long long)blockIdx.x - b.block0[j]) * 256 + threadIdx.x, n = b.row0[j + 1] - b.row0[j];
+  double m[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  if (r < n) {
+    double v[3];
+    affine_point(pts, b.src0[j] + r, M + j * 9, v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) m[c] = m[3 + c] = __dmul_rn(v[c], scale);
+  }
+  block_minmax6(m, red);
+  if (threadIdx.x < 6) part[(long long)blockIdx.x * 6 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// 2. one block per sample: the min / max of its blocks -> offset[sample][3] (sk_dataset.py:154-157); clears its counter
+__global__ void __launch_bounds__(256) voxel_offset_batch_kernel(VoxelBatch b, const double* __restrict__ part,
+                                                                 const double* __restrict__ rnd /*[S,6]*/, double full,
+                                                                 double* __restrict__ offset /*[S,3]*/,
+                                                                 int* __restrict__ n_invalid /*[S]*/) {
+  __shared__ double red[6][4];
+  const int s = blockIdx.x;
+  double v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  for (long long blk = b.block0[s] + threadIdx.x; blk < b.block0[s + 1]; blk += 256)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      v[j] = fmin(v[j], part[blk * 6 + j]);
+      v[3 + j] = fmax(v[3 + j], part[blk * 6 + 3 + j]);
+    }
+  block_minmax6(v, red);
+  if (threadIdx.x < 3) {
+    const int j = threadIdx.x;
+    const double cmin = red[j][0], cmax = red[3 + j][0];
+    double a = __dadd_rn(__dadd_rn(__dadd_rn(full, -cmax), cmin), -0.001);
+    double c = __dadd_rn(__dadd_rn(__dadd_rn(full, -cmax), cmin), 0.001);
+    a = a < 0.0 ? 0.0 : a;
+    c = c > 0.0 ? 0.0 : c;
+    offset[s * 3 + j] = __dadd_rn(__dadd_rn(-cmin, __dmul_rn(a, rnd[s * 6 + j])), __dmul_rn(c, rnd[s * 6 + 3 + j]));
+  }
+  if (threadIdx.x == 3) n_invalid[s] = 0;
+}
+
+// 3. key = sample << 39 | x << 26 | y << 13 | z and the concatenated row as value; points outside the grid counted per sample
+__global__ void __launch_bounds__(256) voxel_keys_batch_kernel(VoxelBatch b, const float* __restrict__ pts,
+                                                               const double* __restrict__ M, double scale,
+                                                               const double* __restrict__ offset, int full,
+                                                               uint64_t* __restrict__ keys, int* __restrict__ vals,
+                                                               int* __restrict__ n_invalid) {
+  const int j = job_of(b.block0, b.n_samples, blockIdx.x);
+  const long long r = ((long long)blockIdx.x - b.block0[j]) * 256 + threadIdx.x, n = b.row0[j + 1] - b.row0[j];
+  if (r >= n) return;
+  double v[3];
+  affine_point(pts, b.src0[j] + r, M + j * 9, v);
+  uint64_t key = (uint64_t)j;
+  bool bad = false;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double x = __dadd_rn(__dmul_rn(v[c], scale), offset[j * 3 + c]);
+    bad |= !(x >= 0.0) || !(x < (double)full);          // sk_dataset.py:160-161 validity assert
+    const int64_t q = (int64_t)x;                        // astype(int): truncation
+    key = (key << 13) | (uint64_t)(q & 0x1FFF);
+  }
+  const long long i = b.row0[j] + r;
+  keys[i] = key;
+  vals[i] = (int)i;
+  if (bad) atomicAdd(n_invalid + j, 1);
+}
+
+// 4. after the stable sort: run heads -> the collated rows.  coords_v_b[run] = unpacked key with the sample in column 3,
+// unique_idx[run] = first occurrence (concatenated row), feats_v_b[run] = that point's feature row, inverse_b[row] = run,
+// voxel_ptr[s] = the run of sample s's first key (the next sample's for a sample without points; the total at the end).
+__global__ void __launch_bounds__(kBlock) rows_compact_batch_kernel(VoxelBatch b, const uint64_t* __restrict__ skeys,
+                                                                    const int* __restrict__ sidx, int64_t n,
+                                                                    const int64_t* __restrict__ offsets, int64_t nblocks,
+                                                                    const float* __restrict__ pts,
+                                                                    const float* __restrict__ inten,
+                                                                    const double* __restrict__ M,
+                                                                    int4* __restrict__ coords_v_b,
+                                                                    float4* __restrict__ feats_v_b,
+                                                                    int64_t* __restrict__ uniq_idx,
+                                                                    int64_t* __restrict__ inverse,
+                                                                    int64_t* __restrict__ voxel_ptr) {
+  __shared__ int wave_cnt[kBlock / 64];
+  const int64_t base = (int64_t)blockIdx.x * kTile;
+  int64_t pos = offsets[blockIdx.x];
+#pragma unroll
+  for (int it = 0; it < kItems; ++it) {
+    const int64_t i = base + it * kBlock + threadIdx.x;
+    const uint64_t v = (i < n) ? skeys[i] : 0;
+    const uint64_t prev = (i < n && i > 0) ? skeys[i - 1] : 0;
+    const bool head = (i < n) && (i == 0 || v != prev);
+    int tot;
+    const int r = block_rank(head, wave_cnt, &tot);
+    if (i < n) {
+      const int64_t run = pos + r - (head ? 0 : 1);
+      const int orig = sidx[i];
+      const int s = (int)(v >> 39);
+      inverse[orig] = run;
+      if (head) {
+        uniq_idx[run] = orig;
+        coords_v_b[run] = make_int4((int)((v >> 26) & 0x1FFF), (int)((v >> 13) & 0x1FFF), (int)(v & 0x1FFF), s);
+        const long long src = b.src0[s] + ((long long)orig - b.row0[s]);
+        double f[3];
+        affine_point(pts, src, M + s * 9, f);
+        feats_v_b[run] = make_float4((float)f[0], (float)f[1], (float)f[2], inten[src]);
+        for (int t = (i == 0 ? 0 : (int)(prev >> 39) + 1); t <= s; ++t) voxel_ptr[t] = run;
+      }
+      if (i == n - 1)
+        for (int t = s + 1; t <= b.n_samples; ++t) voxel_ptr[t] = offsets[nblocks];
+    }
+    pos += tot;
+  }
+}
+
+// min / max partials f64 [blocks, 6] | offsets f64 [S, 3] | keys, sorted keys | rows, sorted rows | scan
+struct VoxelizeBatchWs {
+  double *part, *offset; uint64_t *keys, *skeys; int *ids, *sids, *counts; int64_t* offs; char* sort_tmp;
+  int64_t sort_tmp_bytes, total;
+};
+VoxelizeBatchWs voxelize_batch_layout(int64_t p_total, int n_samples, void* ws) {
+  const int64_t q = p_total > 0 ? p_total : 1, ns = n_samples > 0 ? n_samples : 1;
+  const int64_t blocks = cdiv(q, 256) + ns;          // sum of ceil(p_s / 256) <= p_total / 256 + S
+  const int64_t nb = cdiv(q, kTile), tmp = radix_sort_ws_bytes(q, 8, true);
+  Carver c(ws);
+  return {c.take<double>(6 * blocks), c.take<double>(3 * ns), c.take<uint64_t>(q), c.take<uint64_t>(q), c.take<int>(q),
+          c.take<int>(q), c.take<int>(nb), c.take<int64_t>(nb + 1), c.take(tmp), tmp, c.total()};
+}
+}  // namespace
+
+extern "C" int64_t lidal_voxelize_batch_workspace_bytes(int64_t p_total, int n_samples) {
+  return voxelize_batch_layout(p_total, n_samples, nullptr).total;
+}
+
+extern "C" int lidal_voxelize_batch(const float* points, const float* intensity, const int64_t* src_row0,
+                                    const int64_t* n_points, int n_samples, const double* m_dev, const double* rnd_dev,
+                                    double scale, int full_scale, int32_t* coords_v_b, float* feats_v_b,
+                                    int64_t* unique_idx, int64_t* inverse_b, int64_t* counts_dev, void* ws,
+                                    int64_t ws_bytes, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  LIDAL_REQUIRE(full_scale > 0 && full_scale <= 8192, "voxelize_batch: full_scale must be <= 8192");
+  LIDAL_REQUIRE(n_samples >= 1 && n_samples <= MAX_VOXELIZE_SAMPLES, "voxelize_batch: 1..%d samples, not %d",
+                MAX_VOXELIZE_SAMPLES, n_samples);
+  VoxelBatch b;
+  memset(&b, 0, sizeof(b));
+  b.n_samples = n_samples;
+  long long rows = 0, blocks = 0;
+  for (int j = 0; j < n_samples; ++j) {
+    LIDAL_REQUIRE(n_points[j] >= 0 && src_row0[j] >= 0, "voxelize_batch: sample %d: bad row or point count", j);
+    b.src0[j] = src_row0[j]; b.row0[j] = rows; b.block0[j] = blocks;
+    rows += n_points[j]; blocks += cdiv(n_points[j], 256);
+    LIDAL_REQUIRE(rows < (1ll << 30), "voxelize_batch: %lld points in one batch (fewer than 2^30)", rows);
+  }
+  for (int j = n_samples; j <= MAX_VOXELIZE_SAMPLES; ++j) { b.row0[j] = rows; b.block0[j] = blocks; }
+  int sbits = 0;
+  while ((1 << sbits) < n_samples) ++sbits;
+  int32_t* n_invalid = (int32_t*)(counts_dev + n_samples + 1);
+  if (rows == 0) {                                   // no rows, no error: voxel_ptr and the counters are all zero
+    LIDAL_HIP(hipMemsetAsync(counts_dev, 0, (size_t)(n_samples + 1) * 8 + (size_t)n_samples * 4, s));
+    return 0;
+  }
+  const VoxelizeBatchWs w = voxelize_batch_layout(rows, n_samples, ws);
+  LIDAL_REQUIRE(ws_bytes >= w.total, "voxelize_batch ws too small");
+  const int64_t nb = cdiv(rows, kTile);
+  affine_batch_kernel<<<(unsigned)blocks, 256, 0, s>>>(b, points, m_dev, scale, w.part);
+  LIDAL_CHECK_LAUNCH("affine_batch");
+  voxel_offset_batch_kernel<<<(unsigned)n_samples, 256, 0, s>>>(b, w.part, rnd_dev, (double)full_scale, w.offset, n_invalid);
+  LIDAL_CHECK_LAUNCH("voxel_offset_batch");
+  voxel_keys_batch_kernel<<<(unsigned)blocks, 256, 0, s>>>(b, points, m_dev, scale, w.offset, full_scale, w.keys, w.ids,
+                                                           n_invalid);
+  LIDAL_CHECK_LAUNCH("voxel_keys_batch");
+  if (int rc = radix_sort(w.keys, w.ids, w.skeys, w.sids, rows, 8, 39 + sbits, w.sort_tmp, w.sort_tmp_bytes, s)) return rc;
+  head_count_kernel<<<(unsigned)nb, kBlock, 0, s>>>(w.skeys, rows, w.counts);
+  LIDAL_CHECK_LAUNCH("head_count");
+  scan_counts_kernel<<<1, 1024, 0, s>>>(w.counts, nb, w.offs);
+  LIDAL_CHECK_LAUNCH("scan_counts");
+  rows_compact_batch_kernel<<<(unsigned)nb, kBlock, 0, s>>>(b, w.skeys, w.sids, rows, w.offs, nb, points, intensity, m_dev,
+                                                           (int4*)coords_v_b, (float4*)feats_v_b, unique_idx, inverse_b,
+                                                           counts_dev);
+  LIDAL_CHECK_LAUNCH("rows_compact_batch");
+  return 0;
+}

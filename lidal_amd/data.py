@@ -16,6 +16,11 @@ Supervoxels (dataset/prepare_supervoxel_kmeans_{sk,nu}.py)
 into size-constrained k-means supervoxels in lidal_supervoxel_kmeans and returns the labels with the device CSR the
 scorers and `train_labels` take; `supervoxel_tables` turns the labels into the (sv_id, sv2point) pickles and the id2sv
 list of an existing Processing_files tree; `balanced_assign` is the exact size-constrained assignment on its own.
+
+Whole batches: `voxelize_batch` voxelises and collates up to 32 samples -- the scans of a batch, or
+the augmented views of one scan -- in lidal_voxelize_batch with one read-back; `train_batch`, `val_batch` and
+`score_sample` / `score_frame_inputs` compose it into the three __getitem__ + collate_fn modes of the reference, ending
+in what train_step, evaluate_batches and score_sequence take.
 """
 import math
 
@@ -27,7 +32,8 @@ from . import backend as B
 __all__ = ['draw_augmentation', 'voxelize_scan', 'collate', 'parse_calibration', 'parse_poses',
            'register_scan', 'sk_label_map', 'nu_label_map', 'train_labels', 'train_sample', 'check_labels',
            'labeled_frames', 'frames_from_flag', 'kmeans_supervoxels', 'supervoxel_tables', 'balanced_assign',
-           'supervoxel_bounds', 'supervoxel_costs']
+           'supervoxel_bounds', 'supervoxel_costs', 'voxelize_batch', 'score_sample', 'val_batch', 'train_batch',
+           'score_frame_inputs']
 
 SCALE = 20                # sk_dataset.py:56
 FULL_SCALE = 8192
@@ -234,6 +240,161 @@ def train_sample(points, intensity, raw_labels, label_map, sv_csr=None, sv_flag=
     if not check:
         sample['labels_invalid'] = out[2]
     return sample
+
+
+# ---- a whole batch in one call (sk_dataset.py:143-171 per sample + collate_fn :188-242) --------
+MAX_BATCH_SAMPLES = 32    # csrc/kmap.hip: the sample index rides above the 39 coordinate bits of one sort key
+MAX_BATCH_POINTS = 2 ** 30 - 1            # csrc/sort.hip: fewer than 2^30 items in one sort
+
+
+def _batch_arguments(points, intensity, trans_ms, rnds, full_scale):
+    """The checks of voxelize_batch that need no device -> (shared, points list, intensity list, m f64 [S,9],
+    r f64 [S,6], n_points list).  Everything refused here raises ValueError."""
+    what = 'voxelize_batch'
+    s = len(trans_ms)
+    if s == 0:
+        raise ValueError('%s: no samples' % what)
+    if s > MAX_BATCH_SAMPLES:
+        raise ValueError('%s: %d samples in one call (at most %d)' % (what, s, MAX_BATCH_SAMPLES))
+    if len(rnds) != s:
+        raise ValueError('%s: %d matrices and %d sets of draws' % (what, s, len(rnds)))
+    shared = torch.is_tensor(points)
+    if shared != torch.is_tensor(intensity):
+        raise ValueError('%s: points and intensity are both one tensor (views of one scan) or both lists' % what)
+    pts = [points] if shared else list(points)
+    inten = [intensity] if shared else list(intensity)
+    if not shared and (len(pts) != s or len(inten) != s):
+        raise ValueError('%s: %d point tensors and %d intensity tensors for %d matrices' % (what, len(pts), len(inten), s))
+    for j, (x, w) in enumerate(zip(pts, inten)):
+        if not torch.is_tensor(x) or x.ndim != 2 or x.shape[1] != 3:
+            raise ValueError('%s: sample %d: points must be [P, 3], not %s' % (what, j, tuple(getattr(x, 'shape', ()))))
+        if not torch.is_tensor(w) or w.numel() != x.shape[0]:
+            raise ValueError('%s: sample %d: %d intensities for %d points'
+                             % (what, j, w.numel() if torch.is_tensor(w) else -1, x.shape[0]))
+    m, r = np.empty((s, 9), dtype=np.float64), np.empty((s, 6), dtype=np.float64)
+    for j in range(s):
+        mj, rj = np.asarray(trans_ms[j], dtype=np.float64), np.asarray(rnds[j], dtype=np.float64)
+        if mj.shape != (3, 3):
+            raise ValueError('%s: sample %d: the matrix must be 3 x 3, not %s' % (what, j, mj.shape))
+        if rj.shape != (6,):
+            raise ValueError('%s: sample %d: six uniform draws, not %s' % (what, j, rj.shape))
+        m[j], r[j] = mj.reshape(9), rj
+    if not 0 < int(full_scale) <= 8192:
+        raise ValueError('%s: full_scale=%r must be in 1..8192 (13 bits per axis)' % (what, full_scale))
+    n_points = [pts[0].shape[0]] * s if shared else [x.shape[0] for x in pts]
+    if sum(n_points) > MAX_BATCH_POINTS:
+        raise ValueError('%s: %d points in one call (at most %d)' % (what, sum(n_points), MAX_BATCH_POINTS))
+    return shared, pts, inten, m, r, n_points
+
+
+def voxelize_batch(points, intensity, trans_ms, rnds, scale=SCALE, full_scale=FULL_SCALE):
+    """S = len(trans_ms) samples voxelised AND collated in one library call with one read-back: what S calls of
+    voxelize_scan followed by collate return, bit for bit.
+      points / intensity   lists of S GPU tensors f32 [P_s,3] / [P_s] (the scans of a batch), or ONE tensor each: S views
+                           of the same scan (the score mode, sk_dataloader.py:199-203)
+      trans_ms / rnds      S host matrices 3x3 and S x six draws (draw_augmentation), one pair per sample
+    Returns the dict of collate -- coords_v_b i32 [N,4], feats_v_b f32 [N,4], inverse_indices_b i64 [sum P] (labels_v_b and
+    labels_p_b None) -- plus unique_idxs_b i64 [N] (first occurrences as rows of the concatenated point list) and, on
+    the host, voxel_ptr i64 [S+1] and point_ptr i64 [S+1]: sample s owns voxels voxel_ptr[s]:voxel_ptr[s+1] and points
+    point_ptr[s]:point_ptr[s+1].  ValueError, before anything touches the device, for no samples, more than 32, lengths
+    that do not match and matrices or draws of the wrong shape; AssertionError naming the sample for points outside the
+    grid (sk_dataset.py:161)."""
+    shared, pts, inten, m, r, n_points = _batch_arguments(points, intensity, trans_ms, rnds, full_scale)
+    B.require_gpu(*pts, *inten)
+    s = len(n_points)
+    pts = [x.contiguous().float() for x in pts]
+    inten = [w.contiguous().float().reshape(-1) for w in inten]
+    point_ptr = np.concatenate([[0], np.cumsum(n_points)]).astype(np.int64)
+    p_total = int(point_ptr[-1])
+    src = pts[0] if len(pts) == 1 else torch.cat(pts)
+    src_i = inten[0] if len(inten) == 1 else torch.cat(inten)
+    src_row0 = np.zeros(s, dtype=np.int64) if shared else point_ptr[:-1].copy()
+    n_rows = np.array(n_points, dtype=np.int64)
+    dev = src.device
+    aug = torch.from_numpy(np.concatenate([m.reshape(-1), r.reshape(-1)])).to(dev)          # one upload: [S,9] | [S,6]
+    cap = max(p_total, 1)
+    coords = B.empty((cap, 4), torch.int, dev)
+    feats = B.empty((cap, 4), torch.float32, dev)
+    uniq = B.empty(cap, torch.int64, dev)
+    inverse = B.empty(p_total, torch.int64, dev)
+    counts = torch.empty(s + 1 + (s + 1) // 2, dtype=torch.int64, device=dev)        # voxel_ptr [S+1] | n_invalid i32 [S]
+    ws_bytes = B.lib().lidal_voxelize_batch_workspace_bytes(p_total, s)
+    ws = B.workspace(ws_bytes, dev)
+    B.check(B.lib().lidal_voxelize_batch(B.ptr(src), B.ptr(src_i), src_row0.ctypes.data, n_rows.ctypes.data, s,
+                                         B.ptr(aug), B.ptr(aug[9 * s:]), float(scale), int(full_scale), B.ptr(coords),
+                                         B.ptr(feats), B.ptr(uniq), B.ptr(inverse), B.ptr(counts), B.ptr(ws), ws_bytes,
+                                         B.stream()), 'voxelize_batch')
+    host = counts.cpu().numpy()                                                        # the one read-back
+    voxel_ptr, bad = host[:s + 1].copy(), host[s + 1:].view(np.int32)[:s]
+    if bad.any():                                                                      # sk_dataset.py:161
+        j = int(np.nonzero(bad)[0][0])
+        raise AssertionError('input voxels are not valid: sample %d has %d points outside the grid' % (j, int(bad[j])))
+    n = int(voxel_ptr[-1])
+    return {'coords_v_b': coords[:n], 'feats_v_b': feats[:n], 'labels_v_b': None, 'labels_p_b': None,
+            'inverse_indices_b': inverse, 'unique_idxs_b': uniq[:n], 'voxel_ptr': voxel_ptr, 'point_ptr': point_ptr}
+
+
+def score_sample(points, intensity, inf_reps=8, rng=np.random):
+    """The reference's score batch (sk_dataloader.py:199-203): `inf_reps` __getitem__ calls on ONE scan, each with its
+    own draws (draw_augmentation(rng), in order), collated -- one voxelize_batch of views.  What infer_frame takes."""
+    draws = [draw_augmentation(rng) for _ in range(int(inf_reps))]
+    return voxelize_batch(points, intensity, [d[0] for d in draws], [d[1] for d in draws])
+
+
+def _batch_scans(scans, others, what):
+    scans = list(scans)
+    for name, other in others:
+        if other is not None and len(other) != len(scans):
+            raise ValueError('%s: %d scans and %d %s' % (what, len(scans), len(other), name))
+    return scans
+
+
+def val_batch(scans, raw_labels, label_map, rng=np.random):
+    """The reference's validation batch (mode 'val' + collate_fn): scans is a list of (points, intensity) GPU pairs and
+    raw_labels their annotation arrays (train_labels).  Draws per scan in order, one voxelize_batch, train_labels per
+    scan for labels_p, one check_labels -> the batch of evaluate_batches (labels_p_b beside inverse_indices_b)."""
+    scans = _batch_scans(scans, [('label arrays', raw_labels)], 'val_batch')
+    draws = [draw_augmentation(rng) for _ in scans]
+    batch = voxelize_batch([x for x, _ in scans], [w for _, w in scans], [d[0] for d in draws], [d[1] for d in draws])
+    out = [train_labels(raw, label_map, check=False) for raw in raw_labels]
+    batch['labels_p_b'] = torch.cat([o[0] for o in out])
+    check_labels([o[2] for o in out])
+    return batch
+
+
+def train_batch(scans, raw_labels, label_map, sv_csrs=None, sv_flags=None, pseudos=None, rng=np.random, check=True):
+    """The reference's training batch (modes 'train', 'train_sv', 'train_sv_pseudo' + collate_fn): scans is a list of
+    (points, intensity) GPU pairs; raw_labels, sv_csrs, sv_flags and pseudos hold one entry per scan, as train_labels
+    takes them.  Draws per scan in order, one voxelize_batch, train_labels per scan for labels_p (no read-back),
+    labels_v_b = labels_p_b[unique_idxs_b], one check_labels for the batch (check=False: the counters stay in
+    'labels_invalid') -> the batch of train_step."""
+    if (sv_csrs is None) != (sv_flags is None):
+        raise ValueError('train_batch: sv_csrs and sv_flags come together')
+    scans = _batch_scans(scans, [('label arrays', raw_labels), ('supervoxel lists', sv_csrs), ('flag arrays', sv_flags),
+                                 ('pseudo label arrays', pseudos)], 'train_batch')
+    draws = [draw_augmentation(rng) for _ in scans]
+    batch = voxelize_batch([x for x, _ in scans], [w for _, w in scans], [d[0] for d in draws], [d[1] for d in draws])
+    out = [train_labels(raw_labels[j], label_map, sv_csrs[j] if sv_csrs is not None else None,
+                        sv_flags[j] if sv_flags is not None else None, pseudos[j] if pseudos is not None else None,
+                        check=False) for j in range(len(scans))]
+    batch['labels_p_b'] = torch.cat([o[0] for o in out])
+    batch['labels_v_b'] = batch['labels_p_b'][batch['unique_idxs_b']]
+    if check:
+        check_labels([o[2] for o in out])
+    else:
+        batch['labels_invalid'] = [o[2] for o in out]
+    return batch
+
+
+def score_frame_inputs(points, intensity, pose, sv2point, inf_reps=8, rng=np.random):
+    """One frame of score_sequence from a raw scan: score_sample for the `inf_reps` collated views, register_scan for
+    the world-frame points and sv_csr for the supervoxel lists -> {'coords', 'feats', 'inverse', 'world', 'sv_ptr',
+    'sv_idx'}."""
+    from .score.interframe import sv_csr
+    batch = score_sample(points, intensity, inf_reps, rng)
+    sv_ptr, sv_idx, _ = sv_csr(sv2point, points.device)
+    return {'coords': batch['coords_v_b'], 'feats': batch['feats_v_b'], 'inverse': batch['inverse_indices_b'],
+            'world': register_scan(points, pose), 'sv_ptr': sv_ptr, 'sv_idx': sv_idx}
 
 
 def labeled_frames(sv_flags_per_frame):
