@@ -774,6 +774,30 @@ int lidal_transpose_f32(const float* src, int64_t src_stride, float* dst, int ro
  * input of the stem under bf16: 8-byte rows padded to one 16-byte vector, nn/functional/conv.py _pad_channels). */
 int lidal_cast_rows_bf16(const float* src, int c_src, void* dst, int c_dst, int64_t n, void* stream);
 
+/* ---- optimizer ---------------------------------------------------------------------------------------- */
+/* replaces optimizer.step() of torch.optim.Adam (train.py:56,140) for any number of f32 tensors in ONE launch, no
+ * synchronisation, nothing read back (csrc/optim.hip).  Per element, every operation rounded separately in f32
+ * (correctly rounded sqrt and divide, subnormals kept) -- torch's single-tensor Adam:
+ *     g = grad (+ weight_decay * p if weight_decay != 0);   m = m + (g - m) * one_minus_beta1;
+ *     v = v * beta2 + (one_minus_beta2 * g) * g;            den = sqrtf(v) / bias_correction2_sqrt + eps;
+ *     p = p + neg_step_size * (m / den)
+ * with the scalars, computed by the host in double, cast to float here: bias_correction2_sqrt = sqrt(1 - beta2^t),
+ * neg_step_size = -(lr / (1 - beta1^t)).
+ * `table` (device): records of five 64-bit words, one per tensor --
+ *     { address of p,  gradient's byte offset from grad_base,  first element of its m / v in the flat f32 state buffers
+ *       `m` / `v` [state_numel],  vstart,  n elements }
+ * -- of which the launch updates records [rec_begin, rec_end).  vstart places the tensor on a virtual element axis that
+ * the kernel cuts into chunks of lidal_adam_chunk_elems() elements (vstart ascending with the record index, ranges
+ * disjoint, gaps allowed; 16-byte accesses wherever the addresses of p, gradient and state share one 16-byte phase,
+ * which vstart = address of p / 4 mod 32 = state offset mod 32 arranges for the chunks' boundaries too); [v_begin, v_end)
+ * covers the virtual ranges of the launch's records.  grad_base: NULL with absolute gradient addresses in the table,
+ * or the address the table's offsets are relative to (a flat gradient buffer that is a fresh allocation every step:
+ * the table stays as it is).  A record whose state range leaves [0, state_numel) is skipped. */
+int lidal_adam_chunk_elems(void);
+int lidal_adam_step(const void* table, int rec_begin, int rec_end, int64_t v_begin, int64_t v_end, const void* grad_base,
+                    float* m, float* v, int64_t state_numel, double one_minus_beta1, double beta2, double one_minus_beta2,
+                    double bias_correction2_sqrt, double eps, double neg_step_size, double weight_decay, void* stream);
+
 /* ---- launch plans ----------------------------------------------------------------------------------- */
 /* A whole forward or backward pass as ONE call: `words` is a stream of n_ops operations,
  *     kind | flags << 16,  arg 0, arg 1, ...

@@ -176,6 +176,8 @@ SIGNATURES = {
     'lidal_add2d': (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp]),
     'lidal_transpose_f32': (_i32, [_vp, _i64, _vp, _i32, _i32, _vp]),
     'lidal_cast_rows_bf16': (_i32, [_vp, _i32, _vp, _i32, _i64, _vp]),
+    'lidal_adam_chunk_elems': (_i32, []),
+    'lidal_adam_step': (_i32, [_vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _vp]),
     'lidal_plan_op_args': (_i32, [_i32]),
     'lidal_debug_read': (_i32, [_vp, _vp, _i64]),
     'lidal_plan_run': (_i32, [_vp, _i64, _i64, _vp, _vp]),

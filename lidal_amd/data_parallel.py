@@ -26,6 +26,8 @@ Same gradients as DDP (mean over ranks, scaled before the sum); `state_dict()` c
 import torch
 import torch.distributed as dist
 
+from .flat import BackToBack
+
 __all__ = ['DataParallel']
 
 import os as _os
@@ -44,7 +46,7 @@ class DataParallel(torch.nn.Module):
         self.world = dist.get_world_size(process_group)
         self._queued = False
         self._touched = False
-        self._layout = None             # (address offsets of the gradients, index of the lowest, elements) once they lay back to back
+        self._layout = BackToBack()     # (address offsets of the gradients, index of the lowest, elements) once they lay back to back
         self._params = [p for p in module.parameters() if p.requires_grad]
         self.reductions = 0             # backward passes reduced
         self.flat_reductions = 0        # ... of which in place on one flat buffer
@@ -103,33 +105,9 @@ class DataParallel(torch.nn.Module):
         self._arm(None)                 # (a module whose outputs are not tensors / tuples of tensors)
 
     def _back_to_back(self, grads):
-        """The gradients as ONE tensor if they are contiguous f32 views lying back to back (gaps of less than 16 bytes:
-        16-byte slots) in one storage -- the planned step's flat buffer -- else None.  The full check (dtype, layout,
-        storage, order) runs once; afterwards a step only compares the 161 addresses with the layout found then
-        (25 us instead of 1 ms of Python on a host-bound step)."""
-        g0 = grads[0]
-        lay = self._layout
-        if lay is not None and len(grads) == len(lay[0]):
-            rel, lo_index, span = lay
-            base = grads[lo_index].data_ptr()
-            st = grads[lo_index].untyped_storage()
-            if ([g.data_ptr() - base for g in grads] == rel and 0 <= base - st.data_ptr()
-                    and base - st.data_ptr() + 4 * span <= st.nbytes()):
-                return torch.empty(0, dtype=torch.float32, device=g0.device).set_(st, (base - st.data_ptr()) // 4, (span,))
-        self._layout = None
-        if any(g.dtype != torch.float32 or not g.is_contiguous() or g.device != g0.device for g in grads):
-            return None
-        st = g0.untyped_storage()
-        if any(g.untyped_storage().data_ptr() != st.data_ptr() for g in grads):
-            return None
-        spans = sorted((g.storage_offset(), g.numel(), i) for i, g in enumerate(grads))
-        for (a, n, _), (b, _, _) in zip(spans, spans[1:]):
-            if not 0 <= b - (a + n) < 4:
-                return None
-        lo, hi = spans[0][0], spans[-1][0] + spans[-1][1]
-        base = grads[spans[0][2]].data_ptr()
-        self._layout = ([g.data_ptr() - base for g in grads], spans[0][2], hi - lo)
-        return torch.empty(0, dtype=torch.float32, device=g0.device).set_(st, lo, (hi - lo,))
+        """The gradients as ONE tensor if they lie back to back in one storage -- the planned step's flat buffer --
+        else None (flat.BackToBack: the full check once, then an address comparison per step)."""
+        return self._layout.flat(grads)
 
     def _reduce(self):
         self._queued = False
