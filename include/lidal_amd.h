@@ -831,6 +831,12 @@ int lidal_plan_op_args(int kind);
 int lidal_debug_read(const void* dev, void* host, int64_t nbytes);
 int lidal_plan_run(const int64_t* words, int64_t n_words, int64_t n_ops, void* stream, void* side_stream);
 int lidal_plan_run_streams(const int64_t* words, int64_t n_words, int64_t n_ops, void* const* streams, int n_streams);
+/* A LIDAL_OP_FORK_SIDE directly behind an operation of the main stream makes its side stream wait for that operation's
+ * last LAUNCH (the event rides on the launch: no marker on the main stream); where the operation in front cannot carry
+ * the event -- it ran on a side stream, its last launch does not take one, the fork opens the plan -- the fork records a
+ * marker behind it.  Same ordering either way.  out[0] = forks attached to a launch, out[1] = forks that recorded a
+ * marker, both since the process started or since the last call with out == NULL, which resets them. */
+int lidal_plan_fork_counts(int64_t out[2]);
 
 #ifdef __cplusplus
 }

@@ -182,6 +182,7 @@ SIGNATURES = {
     'lidal_debug_read': (_i32, [_vp, _vp, _i64]),
     'lidal_plan_run': (_i32, [_vp, _i64, _i64, _vp, _vp]),
     'lidal_plan_run_streams': (_i32, [_vp, _i64, _i64, _vp, _i32]),
+    'lidal_plan_fork_counts': (_i32, [_vp]),
 }
 
 
@@ -501,6 +502,16 @@ def side_stream(device, which=1):
         # (the weight gradients' stream as a high-priority queue: measured in round 6, profiles/README.md, not kept)
         _side_streams[key] = torch.cuda.Stream(device=device)
     return _side_streams[key]
+
+
+def plan_fork_counts(reset=False):
+    """(forks of launch plans that waited for their producer's launch, forks that recorded a marker on the main stream)
+    since the process started or since the last reset."""
+    out = (ctypes.c_int64 * 2)()
+    lib_handle().lidal_plan_fork_counts(out)
+    if reset:
+        lib_handle().lidal_plan_fork_counts(None)
+    return int(out[0]), int(out[1])
 
 
 def join_side_streams():

@@ -826,8 +826,8 @@ int bn_bwd(const void* x, const void* dy, int64_t ldy, int64_t n, int c, const f
     bn_bwd_tiles_final_kernel<<<(unsigned)c, NT, 0, s>>>(sums, parts, c, gbeta, ggamma);
     LIDAL_CHECK_LAUNCH("bn_bwd_final(slabs)");
     if (dx != nullptr) {
-      bn_bwd_dx_kernel<T><<<parts, NT, 0, s>>>((const T*)x, (const T*)dy, n, c, mean, invstd, gamma, beta, relu, gbeta,
-                                               ggamma, (T*)dx, rows_per_wg_ew(n, rb), ldy);
+      launch_tail(bn_bwd_dx_kernel<T>, dim3(parts), dim3(NT), 0, s, (const T*)x, (const T*)dy, n, c, mean, invstd, gamma, beta,
+                  relu, gbeta, ggamma, (T*)dx, rows_per_wg_ew(n, rb), ldy);
       LIDAL_CHECK_LAUNCH("bn_bwd_dx");
     }
     return 0;
@@ -843,9 +843,8 @@ int bn_bwd(const void* x, const void* dy, int64_t ldy, int64_t n, int c, const f
   bn_bwd_final_kernel<<<(unsigned)cdiv(c, 8), NT, 0, s>>>(part, np, c, gbeta, ggamma);
   LIDAL_CHECK_LAUNCH("bn_bwd_final");
   if (dx != nullptr) {
-    bn_bwd_dx_kernel<T><<<nslabs_ew(n, (int64_t)c * sizeof(T)), NT, 0, s>>>((const T*)x, (const T*)dy, n, c, mean, invstd,
-                                                    gamma, beta, relu, gbeta, ggamma, (T*)dx,
-                                                    rows_per_wg_ew(n, (int64_t)c * sizeof(T)), ldy);
+    launch_tail(bn_bwd_dx_kernel<T>, dim3(nslabs_ew(n, (int64_t)c * sizeof(T))), dim3(NT), 0, s, (const T*)x, (const T*)dy, n, c,
+                mean, invstd, gamma, beta, relu, gbeta, ggamma, (T*)dx, rows_per_wg_ew(n, (int64_t)c * sizeof(T)), ldy);
     LIDAL_CHECK_LAUNCH("bn_bwd_dx");
   }
   return 0;
@@ -858,11 +857,11 @@ int bn_bwd_masked_partials(const void* out, const void* g, void* gm, int64_t n, 
   constexpr int VEC = IO<T>::VEC;
   const int np = nparts_for(n);
   if (xb != nullptr)
-    bn_bwd_partial_masked_kernel<T, true><<<np, NT, 2 * NT * VEC * sizeof(double), s>>>(
+    launch_tail(bn_bwd_partial_masked_kernel<T, true>, dim3(np), dim3(NT), (unsigned)(2 * NT * VEC * sizeof(double)), s,
         (const T*)out, (const T*)g, (T*)gm, n, c, (const T*)xa, mean_a, invstd_a, part_a, (const T*)xb, mean_b, invstd_b,
         part_b, rows_per_wg(n));
   else
-    bn_bwd_partial_masked_kernel<T, false><<<np, NT, 2 * NT * VEC * sizeof(double), s>>>(
+    launch_tail(bn_bwd_partial_masked_kernel<T, false>, dim3(np), dim3(NT), (unsigned)(2 * NT * VEC * sizeof(double)), s,
         (const T*)out, (const T*)g, (T*)gm, n, c, (const T*)xa, mean_a, invstd_a, part_a, nullptr, nullptr, nullptr,
         nullptr, rows_per_wg(n));
   LIDAL_CHECK_LAUNCH("bn_bwd_partial_masked");
@@ -881,9 +880,8 @@ int bn_bwd_from_partials(const void* x, const void* dy, int64_t ldy, int64_t n, 
   bn_bwd_final_kernel<<<(unsigned)cdiv(c, 8), NT, 0, s>>>(part, nparts_for(n), c, gbeta, ggamma);
   LIDAL_CHECK_LAUNCH("bn_bwd_final");
   if (dx != nullptr) {
-    bn_bwd_dx_kernel<T><<<nslabs_ew(n, (int64_t)c * sizeof(T)), NT, 0, s>>>((const T*)x, (const T*)dy, n, c, mean, invstd,
-                                                    gamma, beta, relu, gbeta, ggamma, (T*)dx,
-                                                    rows_per_wg_ew(n, (int64_t)c * sizeof(T)), ldy);
+    launch_tail(bn_bwd_dx_kernel<T>, dim3(nslabs_ew(n, (int64_t)c * sizeof(T))), dim3(NT), 0, s, (const T*)x, (const T*)dy, n, c,
+                mean, invstd, gamma, beta, relu, gbeta, ggamma, (T*)dx, rows_per_wg_ew(n, (int64_t)c * sizeof(T)), ldy);
     LIDAL_CHECK_LAUNCH("bn_bwd_dx");
   }
   return 0;
@@ -1397,12 +1395,13 @@ bool bn_bwd_merge_dx(const void* x, const void* dy, int64_t ldy, int64_t n, int 
                      const void* part, int nparts, hipStream_t s) {
   Slots slots;
   if (dx == nullptr || !bn_fused() || c > SLOT_CH || !next_slots(&slots, s)) return false;
+  // (the last launch of every BatchNorm backward that takes this form: it carries a pending fork event, launch_tail)
   if (relu)
-    bn_bwd_dx_merge_kernel<T, TILES, true><<<nslabs_ew(n, (int64_t)c * sizeof(T)), NT, 0, s>>>(
+    launch_tail(bn_bwd_dx_merge_kernel<T, TILES, true>, dim3(nslabs_ew(n, (int64_t)c * sizeof(T))), dim3(NT), 0, s,
         (const T*)x, (const T*)dy, n, c, mean, invstd, gamma, beta, relu, part, nparts, gbeta, ggamma, (T*)dx,
         rows_per_wg_ew(n, (int64_t)c * sizeof(T)), ldy, slots);
   else
-    bn_bwd_dx_merge_kernel<T, TILES, false><<<nslabs_ew(n, (int64_t)c * sizeof(T)), NT, 0, s>>>(
+    launch_tail(bn_bwd_dx_merge_kernel<T, TILES, false>, dim3(nslabs_ew(n, (int64_t)c * sizeof(T))), dim3(NT), 0, s,
         (const T*)x, (const T*)dy, n, c, mean, invstd, gamma, beta, relu, part, nparts, gbeta, ggamma, (T*)dx,
         rows_per_wg_ew(n, (int64_t)c * sizeof(T)), ldy, slots);
   return true;
@@ -1425,7 +1424,7 @@ extern "C" int lidal_bn_train_fwd_tiles(const void* x, int dtype, int64_t n, int
   if (bn_fused() && c <= SLOT_CH && next_slots(&slots, s)) {
     const int flags = (relu & 1) | (residual != nullptr ? 2 : 0) | ((residual != nullptr && (relu & 2)) ? 4 : 0);
 #define LIDAL_APPLY_TILES(T, FV)                                                                                          \
-    bn_apply_tiles_kernel<T, EW_THREADS, FV><<<nslabs_ew(n, (int64_t)c * sizeof(T)), EW_THREADS, 0, s>>>(                 \
+    launch_tail(bn_apply_tiles_kernel<T, EW_THREADS, FV>, dim3(nslabs_ew(n, (int64_t)c * sizeof(T))), dim3(EW_THREADS), 0, s, \
         (const T*)x, n, c, tile_stats, (int)n_tiles, eps, momentum, save_mean, save_invstd, running_mean, running_var,    \
         (long long*)num_batches_tracked, gamma, beta, (const T*)residual, (T*)y, rows_per_wg_ew(n, (int64_t)c * sizeof(T)), \
         slots)
@@ -1446,15 +1445,13 @@ extern "C" int lidal_bn_train_fwd_tiles(const void* x, int dtype, int64_t n, int
                                                    (long long*)num_batches_tracked);
   LIDAL_CHECK_LAUNCH("bn_stats_final(tiles)");
   if (dtype == LIDAL_F32)
-    bn_apply_kernel<float, false><<<nslabs_ew(n, (int64_t)c * 4), NT, 0, s>>>((const float*)x, n, c, save_mean, save_invstd,
-                                                              gamma, beta, eps, relu,
-                                                              (const float*)residual, (float*)y,
-                                                              rows_per_wg_ew(n, (int64_t)c * 4));
+    launch_tail(bn_apply_kernel<float, false>, dim3(nslabs_ew(n, (int64_t)c * 4)), dim3(NT), 0, s, (const float*)x, n, c,
+                save_mean, save_invstd, gamma, beta, eps, relu, (const float*)residual, (float*)y,
+                rows_per_wg_ew(n, (int64_t)c * 4));
   else
-    bn_apply_kernel<__bf16, false><<<nslabs_ew(n, (int64_t)c * 2), NT, 0, s>>>((const __bf16*)x, n, c, save_mean,
-                                                               save_invstd, gamma, beta, eps, relu,
-                                                               (const __bf16*)residual, (__bf16*)y,
-                                                               rows_per_wg_ew(n, (int64_t)c * 2));
+    launch_tail(bn_apply_kernel<__bf16, false>, dim3(nslabs_ew(n, (int64_t)c * 2)), dim3(NT), 0, s, (const __bf16*)x, n, c,
+                save_mean, save_invstd, gamma, beta, eps, relu, (const __bf16*)residual, (__bf16*)y,
+                rows_per_wg_ew(n, (int64_t)c * 2));
   LIDAL_CHECK_LAUNCH("bn_apply");
   return 0;
 }
@@ -1558,8 +1555,8 @@ extern "C" int lidal_add_relu_bwd_bn_tile_sums(const void* out, const void* g, v
   const int rpw = rows_per_wg_ew(n, row_bytes);
   const unsigned grid = (unsigned)n_parts;
 #define LIDAL_TAIL(T, DUALV)                                                                                         \
-  tail_tile_sums_kernel<T, DUALV><<<grid, NT, 0, s>>>((const T*)out, (const T*)g, (T*)gm, n, c, (const T*)x_a, mean_a, \
-                                                      invstd_a, sums_a, (const T*)x_b, mean_b, invstd_b, sums_b, rpw)
+  launch_tail(tail_tile_sums_kernel<T, DUALV>, dim3(grid), dim3(NT), 0, s, (const T*)out, (const T*)g, (T*)gm, n, c,  \
+              (const T*)x_a, mean_a, invstd_a, sums_a, (const T*)x_b, mean_b, invstd_b, sums_b, rpw)
   if (dtype == LIDAL_F32) { if (x_b) LIDAL_TAIL(float, true); else LIDAL_TAIL(float, false); }
   else { if (x_b) LIDAL_TAIL(__bf16, true); else LIDAL_TAIL(__bf16, false); }
 #undef LIDAL_TAIL
@@ -1588,13 +1585,13 @@ extern "C" int lidal_bn_bwd_tiles(const void* x, const void* dy, int64_t dy_stri
   LIDAL_CHECK_LAUNCH("bn_bwd_final(tiles)");
   if (dx != nullptr) {
     if (dtype == LIDAL_F32)
-      bn_bwd_dx_kernel<float><<<nslabs_ew(n, (int64_t)c * 4), NT, 0, s>>>((const float*)x, (const float*)dy, n, c, save_mean,
-                                                          save_invstd, gamma, beta, relu, grad_beta, grad_gamma,
-                                                          (float*)dx, rows_per_wg_ew(n, (int64_t)c * 4), dy_stride);
+      launch_tail(bn_bwd_dx_kernel<float>, dim3(nslabs_ew(n, (int64_t)c * 4)), dim3(NT), 0, s, (const float*)x, (const float*)dy,
+                  n, c, save_mean, save_invstd, gamma, beta, relu, grad_beta, grad_gamma, (float*)dx,
+                  rows_per_wg_ew(n, (int64_t)c * 4), dy_stride);
     else
-      bn_bwd_dx_kernel<__bf16><<<nslabs_ew(n, (int64_t)c * 2), NT, 0, s>>>((const __bf16*)x, (const __bf16*)dy, n, c, save_mean,
-                                                           save_invstd, gamma, beta, relu, grad_beta, grad_gamma,
-                                                           (__bf16*)dx, rows_per_wg_ew(n, (int64_t)c * 2), dy_stride);
+      launch_tail(bn_bwd_dx_kernel<__bf16>, dim3(nslabs_ew(n, (int64_t)c * 2)), dim3(NT), 0, s, (const __bf16*)x,
+                  (const __bf16*)dy, n, c, save_mean, save_invstd, gamma, beta, relu, grad_beta, grad_gamma, (__bf16*)dx,
+                  rows_per_wg_ew(n, (int64_t)c * 2), dy_stride);
     LIDAL_CHECK_LAUNCH("bn_bwd_dx");
   }
   return 0;
@@ -1679,7 +1676,7 @@ extern "C" int lidal_colsum(const void* x, int dtype, int64_t n, int c, float* o
   else
     colsum_partial_kernel<__bf16><<<np, NT, NT * 8 * sizeof(double), s>>>((const __bf16*)x, n, c, part, rows_per_wg(n));
   LIDAL_CHECK_LAUNCH("colsum_partial");
-  bn_bwd_final_kernel<<<(unsigned)cdiv(c, 8), NT, 0, s>>>(part, np, c, out, scratch);
+  launch_tail(bn_bwd_final_kernel, dim3((unsigned)cdiv(c, 8)), dim3(NT), 0, s, part, np, c, out, scratch);
   LIDAL_CHECK_LAUNCH("colsum_final");
   return 0;
 }

@@ -1,6 +1,7 @@
 // Shared helpers for liblidal_amd.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -35,6 +36,26 @@ void set_error(const char* fmt, ...);
       return 1;                                                               \
     }                                                                         \
   } while (0)
+
+// ---- the tail event: a side-stream fork that rides on its producer's launch (plan.hip, run_ops) ----
+// The plan runner sets an event before it dispatches an operation whose successor is a fork.  The operation's LAST launch
+// goes through launch_tail, which takes the event and hands it to the launch as its completion event: the side stream
+// then waits for that launch itself, and the producing queue carries no marker packet behind it (a marker costs the
+// queue ~5.5 us, an event on the launch ~2 us: scripts/exp/fork_edge_cost.hip).  An operation that does not end in
+// launch_tail leaves the event pending; the runner sees that and records a marker as before.  Thread-local: plans of
+// two host threads do not see each other's event.
+void set_tail_event(hipEvent_t ev);
+hipEvent_t take_tail_event();         // the pending event (and none is pending afterwards), or nullptr
+void clear_tail_event();
+
+// the last kernel an operation puts on its stream; without a pending event exactly kernel<<<grid, block, lds, s>>>(args...)
+template <typename... Formals, typename... Actuals>
+inline void launch_tail(void (*kernel)(Formals...), dim3 grid, dim3 block, unsigned lds, hipStream_t s, Actuals... args) {
+  if (hipEvent_t ev = take_tail_event())
+    hipExtLaunchKernelGGL(kernel, grid, block, lds, s, /*startEvent*/ nullptr, /*stopEvent*/ ev, 0, args...);
+  else
+    kernel<<<grid, block, lds, s>>>(args...);
+}
 
 __host__ __device__ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ static inline int64_t align_up(int64_t a, int64_t b) { return cdiv(a, b) * b; }

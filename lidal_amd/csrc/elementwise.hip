@@ -195,12 +195,12 @@ extern "C" int lidal_add_relu_bwd(const void* y, const void* g, void* gin, int64
   if (numel == 0) return 0;
   if (dtype == LIDAL_F32) {
     LIDAL_REQUIRE(numel % 4 == 0, "add_relu: element count must be a multiple of 4");
-    add_relu_bwd_kernel<float><<<ew_grid(numel / 4), 256, 0, s>>>((const float*)y, (const float*)g,
-                                                                  (float*)gin, numel / 4);
+    launch_tail(add_relu_bwd_kernel<float>, dim3(ew_grid(numel / 4)), dim3(256), 0, s, (const float*)y, (const float*)g,
+                (float*)gin, numel / 4);
   } else if (dtype == LIDAL_BF16) {
     LIDAL_REQUIRE(numel % 8 == 0, "add_relu: element count must be a multiple of 8");
-    add_relu_bwd_kernel<__bf16><<<ew_grid(numel / 8), 256, 0, s>>>((const __bf16*)y, (const __bf16*)g,
-                                                                   (__bf16*)gin, numel / 8);
+    launch_tail(add_relu_bwd_kernel<__bf16>, dim3(ew_grid(numel / 8)), dim3(256), 0, s, (const __bf16*)y, (const __bf16*)g,
+                (__bf16*)gin, numel / 8);
   } else {
     set_error("add_relu: bad dtype %d", dtype);
     return 2;

@@ -17,6 +17,7 @@
 // channel concatenation / padding / slicing, strided sum of two gradients, f32 transposition, f32 -> bf16
 // row cast with channel padding).
 #include <string.h>
+#include <atomic>
 #include <mutex>
 
 #include "common.h"
@@ -132,7 +133,7 @@ extern "C" int lidal_copy2d(const void* src, int64_t src_pitch, void* dst, int64
                        (uint64_t)row_bytes | (uint64_t)zero_bytes;
   LIDAL_REQUIRE(row_bytes + zero_bytes < (1ll << 30), "copy2d: rows too long");
 #define LIDAL_COPY2D(U)                                                                                        \
-  copy2d_kernel<U><<<grid_for(rows * ((row_bytes + zero_bytes) / (int64_t)sizeof(U))), 256, 0, s>>>(          \
+  launch_tail(copy2d_kernel<U>, dim3(grid_for(rows * ((row_bytes + zero_bytes) / (int64_t)sizeof(U)))), dim3(256), 0, s, \
       (const U*)src, src_pitch / (int64_t)sizeof(U), (U*)dst, dst_pitch / (int64_t)sizeof(U), rows,           \
       (int)(row_bytes / (int64_t)sizeof(U)), (int)(zero_bytes / (int64_t)sizeof(U)))
   if (all % 16 == 0) LIDAL_COPY2D(uint4);
@@ -245,23 +246,38 @@ inline double as_double(int64_t w) {
 }
 
 // one pair of events per device and side stream for fork / join (created on first use, never timed).  An edge is
-// "record on A, then make B wait for that record": the wait captures the record it follows, so the same event serves
-// every later edge -- but two host threads running plans on one device must not interleave their record / wait
-// pairs, hence one mutex per device around each pair (and around the creation).
+// "bind the event on A, then make B wait for it": the wait captures the binding it follows, so the same event serves
+// every later edge (measured for both kinds of binding, one event re-bound 200 times: scripts/exp/fork_edge_cost.hip).
+// An event is bound either by a record -- a marker packet on A, which A's next kernel waits for: ~5.5 us of A's time
+// -- or, for a fork, as the completion event of the producing launch itself (the tail event of common.h): ~2 us, and
+// nothing behind the kernel on A.  The events keep the default release scope: hipEventReleaseToDevice was measured on
+// both bindings and changes neither (profiles/r08_fork_edges.txt).
+// INVARIANT: from the moment a thread binds one of these events (hands it to a dispatch as its tail event, or records
+// it) to the last wait that means that binding, the thread holds the device's mutex -- two host threads running plans
+// on one device cannot interleave their bind / wait spans (nor the creation).
 constexpr int MAX_SIDE = 8;
 hipEvent_t g_fork_ev[MAX_DEVICES][MAX_SIDE], g_join_ev[MAX_DEVICES][MAX_SIDE];
 bool g_ev_ready[MAX_DEVICES][MAX_SIDE];
 std::mutex g_ev_mutex[MAX_DEVICES];
+// forks that waited for their producer's launch / forks that recorded a marker (lidal_plan_fork_counts)
+std::atomic<int64_t> g_forks_attached{0}, g_forks_marker{0};
 
-// `to` waits for everything queued on `from` so far (join = false: the fork event of side stream idx, true: its join event)
-int stream_edge(int idx, bool join, hipStream_t from, hipStream_t to) {
-  const int d = current_device();
-  std::lock_guard<std::mutex> lock(g_ev_mutex[d]);
+// (the caller holds g_ev_mutex[d])
+int ensure_events(int d, int idx) {
   if (!g_ev_ready[d][idx]) {
     LIDAL_HIP(hipEventCreateWithFlags(&g_fork_ev[d][idx], hipEventDisableTiming));
     LIDAL_HIP(hipEventCreateWithFlags(&g_join_ev[d][idx], hipEventDisableTiming));
     g_ev_ready[d][idx] = true;
   }
+  return 0;
+}
+
+// `to` waits for everything queued on `from` so far, behind a marker on `from` (join = false: the fork event of side
+// stream idx, true: its join event)
+int stream_edge(int idx, bool join, hipStream_t from, hipStream_t to) {
+  const int d = current_device();
+  std::lock_guard<std::mutex> lock(g_ev_mutex[d]);
+  if (int rc = ensure_events(d, idx)) return rc;
   hipEvent_t ev = join ? g_join_ev[d][idx] : g_fork_ev[d][idx];
   LIDAL_HIP(hipEventRecord(ev, from));
   LIDAL_HIP(hipStreamWaitEvent(to, ev, 0));
@@ -271,6 +287,17 @@ int stream_edge(int idx, bool join, hipStream_t from, hipStream_t to) {
 }  // namespace
 
 extern "C" int lidal_plan_op_args(int kind) { return kind > 0 && kind < kNumOps ? kOps[kind].n_args : -1; }
+
+extern "C" int lidal_plan_fork_counts(int64_t out[2]) {
+  if (out == nullptr) {
+    g_forks_attached = 0;
+    g_forks_marker = 0;
+    return 0;
+  }
+  out[0] = g_forks_attached;
+  out[1] = g_forks_marker;
+  return 0;
+}
 
 extern "C" int lidal_plan_run(const int64_t* words, int64_t n_words, int64_t n_ops, void* stream, void* side_stream) {
   void* streams[2] = {stream, side_stream};
@@ -309,6 +336,17 @@ int run_ops(const int64_t* words, int64_t n_words, int64_t n_ops, void* const* s
 #define I(i) ((int)a[i])
 #define L(i) ((int64_t)a[i])
 #define F(i) ((float)as_double(a[i]))
+  // A fork rides on the launch in front of it.  Before an operation of the MAIN stream is dispatched, the runner looks
+  // one word group ahead: if a fork follows, that fork's event becomes the tail event of the dispatch, and the
+  // operation's last launch completes into it (launch_tail).  The fork -- and every fork directly behind it, whichever
+  // side stream it opens: one event, several waits -- then only makes its side stream wait.  Where the event was not
+  // taken (an operation that does not end in launch_tail or returned without a launch), where the operation ran on a
+  // side stream, or where nothing precedes the fork in this plan, the fork records a marker as before.  `span` is the
+  // device's event mutex, held from the dispatch that binds the event to the last of those waits (the invariant above).
+  const int dev = current_device();
+  std::unique_lock<std::mutex> span(g_ev_mutex[dev], std::defer_lock);
+  hipEvent_t attached = nullptr;          // the event the last main-stream launch completes into; only forks have followed
+  struct TailGuard { ~TailGuard() { clear_tail_event(); } } tail_guard;      // no way out of here leaves one pending
   int64_t pos = 0;
   for (int64_t op = 0; op < n_ops; ++op) {
     LIDAL_REQUIRE(pos < n_words, "plan_run: op %lld starts past the end of the stream (%lld words)", (long long)op,
@@ -326,6 +364,22 @@ int run_ops(const int64_t* words, int64_t n_words, int64_t n_ops, void* const* s
       LIDAL_REQUIRE(sidx < n_streams && streams[sidx] != nullptr && side_open[sidx], "plan_run: op %lld (%s) wants side "
                     "stream %d outside a fork / join bracket", (long long)op, kOps[kind].name, sidx);
       st = streams[sidx];
+    }
+    hipEvent_t tail = nullptr;
+    if (kind != LIDAL_OP_FORK_SIDE) {
+      if (span.owns_lock()) span.unlock();            // the forks behind the last launch have all been served
+      attached = nullptr;
+      if (kind != LIDAL_OP_JOIN_SIDE && sidx == 0 && op + 1 < n_ops && pos < n_words &&
+          (words[pos] & 0xFFFF) == LIDAL_OP_FORK_SIDE) {
+        const int f = (int)((words[pos] >> 16) & 0xF);
+        const int i = f ? f : 1;
+        if (i < n_streams && streams[i] != nullptr) {
+          span.lock();
+          if (int erc = ensure_events(dev, i)) return erc;
+          tail = g_fork_ev[dev][i];
+          set_tail_event(tail);
+        }
+      }
     }
     int rc = 0;
     switch (kind) {
@@ -453,7 +507,13 @@ int run_ops(const int64_t* words, int64_t n_words, int64_t n_ops, void* const* s
         const int i = sidx ? sidx : 1;
         LIDAL_REQUIRE(i < n_streams && streams[i] != nullptr, "plan_run: op %lld forks to side stream %d, which was not "
                       "given", (long long)op, i);
-        if (stream_edge(i, false, (hipStream_t)stream, (hipStream_t)streams[i])) return 1;
+        if (attached != nullptr) {       // the launch in front completes into `attached`: no marker on the main stream
+          LIDAL_HIP(hipStreamWaitEvent((hipStream_t)streams[i], attached, 0));
+          ++g_forks_attached;
+        } else {
+          if (stream_edge(i, false, (hipStream_t)stream, (hipStream_t)streams[i])) return 1;
+          ++g_forks_marker;
+        }
         side_open[i] = true;
         break;
       }
@@ -468,6 +528,10 @@ int run_ops(const int64_t* words, int64_t n_words, int64_t n_ops, void* const* s
       default:
         set_error("plan_run: op %lld: kind %d not handled", (long long)op, kind);
         return 2;
+    }
+    if (tail != nullptr) {
+      if (take_tail_event() == nullptr && rc == 0) attached = tail;       // the operation's last launch took it
+      else span.unlock();                                                 // left pending (cleared now): the fork records a marker
     }
     if (rc != 0) {          // keep the callee's message, say where in the plan it happened
       char msg[400];

@@ -759,6 +759,21 @@ int launch_devox_cells(const T* g, const int* vorder, const int64_t* vseg, const
     }                                                                                        \
   } while (0)
 
+// DISPATCH_TVEC for the one launch of an operation that a launch plan forks behind (launch_tail, common.h)
+#define DISPATCH_TVEC_TAIL(kernel, T, c, total_rows, ...)                                    \
+  do {                                                                                       \
+    if (sizeof(T) == 2 && (c) % 8 == 0) {                                                    \
+      int64_t t__ = (total_rows) * ((c) / 8);                                                \
+      launch_tail(kernel<T, 8>, dim3((unsigned)cdiv(t__, 256)), dim3(256), 0, s, __VA_ARGS__); \
+    } else if ((c) % 4 == 0) {                                                               \
+      int64_t t__ = (total_rows) * ((c) / 4);                                                \
+      launch_tail(kernel<T, 4>, dim3((unsigned)cdiv(t__, 256)), dim3(256), 0, s, __VA_ARGS__); \
+    } else {                                                                                 \
+      int64_t t__ = (total_rows) * (c);                                                      \
+      launch_tail(kernel<T, 1>, dim3((unsigned)cdiv(t__, 256)), dim3(256), 0, s, __VA_ARGS__); \
+    }                                                                                        \
+  } while (0)
+
 extern "C" int lidal_count(const int32_t* idx, int64_t n, int32_t* out, int64_t m, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (m > 0) LIDAL_HIP(hipMemsetAsync(out, 0, 4 * m, s));
@@ -819,11 +834,11 @@ extern "C" int lidal_voxelize_bwd(const void* gout, const int32_t* idx, const in
   hipStream_t s = (hipStream_t)stream;
   if (n == 0 || c == 0) return 0;
   if (dtype == LIDAL_F32)
-    DISPATCH_TVEC(voxelize_bwd_kernel, float, c, n, (const float*)gout, idx, counts,
-                  (const float*)residual, (float*)gin, n, m, c);
+    DISPATCH_TVEC_TAIL(voxelize_bwd_kernel, float, c, n, (const float*)gout, idx, counts,
+                       (const float*)residual, (float*)gin, n, m, c);
   else if (dtype == LIDAL_BF16)
-    DISPATCH_TVEC(voxelize_bwd_kernel, __bf16, c, n, (const __bf16*)gout, idx, counts,
-                  (const __bf16*)residual, (__bf16*)gin, n, m, c);
+    DISPATCH_TVEC_TAIL(voxelize_bwd_kernel, __bf16, c, n, (const __bf16*)gout, idx, counts,
+                       (const __bf16*)residual, (__bf16*)gin, n, m, c);
   else { set_error("voxelize_bwd: bad dtype %d", dtype); return 2; }
   LIDAL_CHECK_LAUNCH("lidal_voxelize_bwd");
   return 0;
@@ -835,9 +850,9 @@ extern "C" int lidal_devoxelize_fwd(const void* feat, const int32_t* idx, const 
   hipStream_t s = (hipStream_t)stream;
   if (n == 0 || c == 0) return 0;
   if (dtype == LIDAL_F32)
-    DISPATCH_TVEC(devoxelize_fwd_kernel, float, c, n, (const float*)feat, idx, w, (float*)out, n, m, c);
+    DISPATCH_TVEC_TAIL(devoxelize_fwd_kernel, float, c, n, (const float*)feat, idx, w, (float*)out, n, m, c);
   else if (dtype == LIDAL_BF16)
-    DISPATCH_TVEC(devoxelize_fwd_kernel, __bf16, c, n, (const __bf16*)feat, idx, w, (__bf16*)out, n, m, c);
+    DISPATCH_TVEC_TAIL(devoxelize_fwd_kernel, __bf16, c, n, (const __bf16*)feat, idx, w, (__bf16*)out, n, m, c);
   else { set_error("devoxelize_fwd: bad dtype %d", dtype); return 2; }
   LIDAL_CHECK_LAUNCH("lidal_devoxelize_fwd");
   return 0;
