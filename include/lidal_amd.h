@@ -553,6 +553,43 @@ int lidal_ce_bwd(const void* logits, int dtype, const int64_t* labels, int64_t n
                  int64_t ignore_index, const float* fwd_out2, const float* grad_scale,
                  void* dlogits, void* stream);
 
+/* ---- objectives beside the plain cross-entropy (csrc/loss.hip; not plan operations: the loss is the caller's) ---- */
+/* The same cross-entropy with class weights, torch.nn.functional.cross_entropy(weight=w, reduction='mean'):
+ * weight f32 [c]; out2 f32 [2] = {sum_i w[y_i] * -log p[i, y_i] / sum_i w[y_i], sum_i w[y_i]} over the non-ignored rows
+ * (no such row, or only zero weights: 0 / 0 = nan, as torch); backward:
+ * dlogits_i = w[y_i] * (softmax_i - onehot) * grad_scale[0] / out2[1], zero on ignored rows.  c in 1..32. */
+int64_t lidal_ce_weighted_workspace_bytes(int64_t n);
+int lidal_ce_weighted_fwd(const void* logits, int dtype, const int64_t* labels, int64_t n, int c, int64_t ignore_index,
+                          const float* weight, float* out2, void* ws, int64_t ws_bytes, void* stream);
+int lidal_ce_weighted_bwd(const void* logits, int dtype, const int64_t* labels, int64_t n, int c, int64_t ignore_index,
+                          const float* weight, const float* fwd_out2, const float* grad_scale, void* dlogits,
+                          void* stream);
+/* Lovasz-softmax (Berman et al., CVPR 2018, lovasz_softmax_flat) over the rows whose label is not ignore_index.
+ * x [n, c]: logits f32 / bf16 (is_probs = 0: the forward pass takes p = softmax in f64 and rounds
+ * e once to f32, the backward pass p = softmax in f32) or probabilities f32 (is_probs = 1).  Per class k:
+ * fg = (label == k), e = |fg - p_k| in f32, rows ordered by e descending, ties by ascending row (ONE stable sort for
+ * all classes, key = k << 32 | ~bits(e)); gts = sum fg; at rank r: inter = gts - cumsum(fg), union = gts + cumsum(1 - fg)
+ * (integers), jac = 1 - inter / union in f32, g[r] = jac[r] - jac[r - 1], g[0] = jac[0]; L_k = sum_r e[r] g[r] in f64.
+ * Outputs:
+ *   out   f64 [4 + 2 c] = {loss, number of present classes (gts > 0), status, valid rows, L_k [c], gts_k [c]};
+ *         loss = mean of L_k over the present classes (mode_all = 0) or over all c classes (mode_all = 1), 0 without a
+ *         valid row or a class that counts; status != 0: some label was outside [0, c) and not ignore_index (such rows
+ *         are left out like ignored ones) -- it travels with the loss, for the caller to read where it reads the loss;
+ *   grad  f32 [n, c] = dL_k / dp[i, k]: -g[rank] where fg = 1, +g[rank] where fg = 0, 0 where e == 0, 0 on ignored rows;
+ *   ranks i32 [n, c] or NULL: the rank of row i in class k's order, -1 on ignored rows.
+ * Backward: with s_k = grad_scale[0] * [class k counts] / (number of classes that count) + grad_class[k] (either
+ * pointer may be NULL: the gradient of the loss, and of the per-class losses L_k), a_k = grad[i, k] * s_k:
+ *   is_probs = 1: dx[i, k] = a_k (f32);     is_probs = 0: dx[i, k] = p_k * (a_k - sum_j a_j p_j), j ascending, in x's
+ *   dtype; zero on ignored rows.
+ * Limits: c in 1..32, n * c < 2^30 (refused before any launch; the workspace size of a refused shape is 0).  No float
+ * atomics: two runs give the same bits. */
+int64_t lidal_lovasz_workspace_bytes(int64_t n, int c);
+int lidal_lovasz_fwd(const void* x, int dtype, int is_probs, const int64_t* labels, int64_t n, int c, int64_t ignore_index,
+                     int mode_all, double* out, float* grad, int32_t* ranks, void* ws, int64_t ws_bytes, void* stream);
+int lidal_lovasz_bwd(const void* x, int dtype, int is_probs, const int64_t* labels, int64_t n, int c, int64_t ignore_index,
+                     int mode_all, const double* out, const float* grad, const float* grad_scale, const float* grad_class,
+                     void* dx, void* stream);
+
 /* ---- probability inference post-processing ------------------------------------------------- */
 /* replaces score/prob_inference.py:100-113: logits f32 [nv, c] of `reps` collated views,
  * inverse i64 [reps*p] (voxel row of every point in every view) -> prob f32 [p,c] = mean over

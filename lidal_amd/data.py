@@ -33,7 +33,7 @@ __all__ = ['draw_augmentation', 'voxelize_scan', 'collate', 'parse_calibration',
            'register_scan', 'sk_label_map', 'nu_label_map', 'train_labels', 'train_sample', 'check_labels',
            'labeled_frames', 'frames_from_flag', 'kmeans_supervoxels', 'supervoxel_tables', 'balanced_assign',
            'supervoxel_bounds', 'supervoxel_costs', 'voxelize_batch', 'score_sample', 'val_batch', 'train_batch',
-           'score_frame_inputs']
+           'score_frame_inputs', 'class_weights']
 
 SCALE = 20                # sk_dataset.py:56
 FULL_SCALE = 8192
@@ -395,6 +395,33 @@ def score_frame_inputs(points, intensity, pose, sv2point, inf_reps=8, rng=np.ran
     sv_ptr, sv_idx, _ = sv_csr(sv2point, points.device)
     return {'coords': batch['coords_v_b'], 'feats': batch['feats_v_b'], 'inverse': batch['inverse_indices_b'],
             'world': register_scan(points, pose), 'sv_ptr': sv_ptr, 'sv_idx': sv_idx}
+
+
+def class_weights(labels_v_b, n_classes, ignore=255, kind='inverse'):
+    """Per-class weights f32 [n_classes] for nn.functional.cross_entropy(weight=...) from the histogram of a label
+    tensor (any shape, integer, on the device; `ignore` and labels outside [0, n_classes) are not counted).  With
+    n_k the count of class k and f_k = n_k / sum_j n_j:
+        'inverse'       w_k = 1 / f_k
+        'inverse_sqrt'  w_k = 1 / sqrt(f_k)
+        'log'           w_k = 1 / log(1.02 + f_k)              (Paszke et al., ENet)
+    A class without a label gets weight 0 under the two inverse kinds (no row carries it anyway) and the formula's
+    finite 1 / log(1.02) under 'log'.  The inverse kinds are then scaled so that the weights of the classes that occur
+    average 1; 'log' is left as the formula gives it.  Computed in f64 from exact counts (lidal_count)."""
+    from .nn.functional.count import spcount
+    if kind not in ('inverse', 'inverse_sqrt', 'log'):
+        raise ValueError("kind must be 'inverse', 'inverse_sqrt' or 'log', got %r" % (kind,))
+    B.require_gpu(labels_v_b)
+    flat = labels_v_b.reshape(-1)
+    idx = torch.where(flat == ignore, torch.full_like(flat, -1), flat).clamp(-1, n_classes).int()
+    counts = spcount(idx, n_classes).double()
+    f = counts / counts.sum().clamp_min(1.0)
+    if kind == 'log':
+        return (1.0 / torch.log(1.02 + f)).float()
+    has = counts > 0
+    w = torch.where(has, 1.0 / f.clamp_min(1e-300), torch.zeros_like(f))
+    if kind == 'inverse_sqrt':
+        w = w.sqrt()
+    return (w / (w.sum() / has.sum().clamp_min(1)).clamp_min(1e-300)).float()
 
 
 def labeled_frames(sv_flags_per_frame):

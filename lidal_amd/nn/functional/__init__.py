@@ -4,12 +4,13 @@ from .conv import KernelMap, build_kernel_map, conv3d
 from .count import spcount
 from .devoxelize import calc_ti_weights, spdevoxelize, ti_weights_and_index
 from .downsample import downsample_pyramid, spdownsample, unique_sorted
-from .fused import add_relu, cross_entropy
+from .fused import add_relu
 from .hash import sphash
+from .loss import combined_loss, cross_entropy, lovasz_forward, lovasz_softmax, lovasz_softmax_flat
 from .query import HashTable, coords_table, sphashquery
 from .voxelize import spvoxelize
 
 __all__ = ['sphash', 'sphashquery', 'HashTable', 'coords_table', 'spcount', 'spvoxelize', 'spdevoxelize',
            'calc_ti_weights', 'ti_weights_and_index', 'spdownsample', 'downsample_pyramid', 'unique_sorted', 'conv3d',
-           'add_relu', 'cross_entropy',
+           'add_relu', 'cross_entropy', 'lovasz_softmax', 'lovasz_softmax_flat', 'lovasz_forward', 'combined_loss',
            'KernelMap', 'build_kernel_map']
