@@ -596,6 +596,14 @@ int lidal_lovasz_bwd(const void* x, int dtype, int is_probs, const int64_t* labe
  * views of softmax(logits[inverse]), pred i64 [p] = argmax. */
 int lidal_view_mean_softmax(const float* logits, const int64_t* inverse, int reps, int64_t p,
                             int c, float* prob, int64_t* pred, void* stream);
+/* The call above plus how much the views DISAGREED about every point, in one launch, no workspace:
+ * LiDAL's formula (score/sv_level/LiDAL.py:59-81) with the point's view mean m = prob[i] in the query frame's place and
+ * its `reps` soft-max rows p_v in the matched neighbours' place.  prob, pred: the same bytes as the call above.
+ *   viewd f64 [p] = (1 / reps) sum_v sum_k kl_div(m_k + 1e-5f, p_vk + 1e-5f)   (f32 terms, numpy's f32 class sum, f64 over views)
+ *   viewe f32 [p] = scipy.stats.entropy(m)
+ *   agree i32 [p] = the views whose logits row has its first maximum at pred[i], 0..reps. */
+int lidal_view_scores(const float* logits, const int64_t* inverse, int reps, int64_t p, int c, float* prob,
+                      int64_t* pred, double* viewd, float* viewe, int32_t* agree, void* stream);
 
 /* replaces evaluate.py:100-109 + utils/iou_sk.py:14-19 ("next" row 8f-4): conf i32 [c*c] +=
  * bincount(argmax(logits[inverse]) * c + labels) over labelled points (label < 100); conf is

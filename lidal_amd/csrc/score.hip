@@ -60,6 +60,93 @@ __global__ void __launch_bounds__(256) view_mean_softmax_kernel(const float* __r
   pred[i] = arg;
 }
 
+// ---------------- disagreement of the views ----------------
+// The soft-max of one gathered logits row, view_mean_softmax_kernel's statements: the probability of class j is
+// x[j] / s.  Returns the class of the row's first maximum.  view_scores_kernel reads every row twice through this and
+// gets the same bits both times.
+__device__ __forceinline__ int view_row_softmax(const float* __restrict__ row, int c, float (&x)[kMaxClasses], float& s) {
+  float mx = -INFINITY;
+  int arg = 0;
+#pragma unroll
+  for (int j = 0; j < kMaxClasses; ++j)
+    if (j < c) {
+      x[j] = row[j];
+      if (x[j] > mx) arg = j;
+      mx = fmaxf(mx, x[j]);
+    }
+  s = 0.f;
+#pragma unroll
+  for (int j = 0; j < kMaxClasses; ++j)
+    if (j < c) { x[j] = expf(x[j] - mx); s += x[j]; }
+  return arg;
+}
+
+// LiDAL.py:59-81 with the point's own view mean m where the query frame stands and its views p_v where the matched
+// neighbours stand: viewd = (1 / reps) sum_v np_sum_f32_k (float)kl_div(m_k + eps, p_vk + eps) in an f64 accumulator,
+// viewe = scipy's entropy(m), agree = the views whose logits row has its first maximum at pred.  prob and pred are
+// view_mean_softmax_kernel's, restated (tests/test_view_scores_gpu.py holds the two to the same bytes).  m needs every
+// view before the first term can be formed, and reps rows of probabilities do not fit registers at a run-time reps: the
+// thread gathers its rows a second time (they are in the caches from the first) and recomputes p_v.
+__global__ void __launch_bounds__(256) view_scores_kernel(const float* __restrict__ logits,
+                                                          const int64_t* __restrict__ inverse, int reps, int64_t p,
+                                                          int c, float* __restrict__ prob, int64_t* __restrict__ pred,
+                                                          double* __restrict__ viewd, float* __restrict__ viewe,
+                                                          int* __restrict__ agree) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p) return;
+  float m[kMaxClasses];
+#pragma unroll
+  for (int j = 0; j < kMaxClasses; ++j) m[j] = 0.f;
+  for (int v = 0; v < reps; ++v) {
+    float x[kMaxClasses];
+    float s;
+    view_row_softmax(logits + inverse[(int64_t)v * p + i] * c, c, x, s);
+#pragma unroll
+    for (int j = 0; j < kMaxClasses; ++j)
+      if (j < c) m[j] = (v == 0) ? (x[j] / s) : __fadd_rn(m[j], x[j] / s);
+  }
+  float best = -INFINITY;
+  int arg = 0;
+  const float inv = (float)reps;
+#pragma unroll
+  for (int j = 0; j < kMaxClasses; ++j)
+    if (j < c) {
+      m[j] = m[j] / inv;
+      prob[i * c + j] = m[j];
+      if (m[j] > best) { best = m[j]; arg = j; }
+    }
+  pred[i] = arg;
+  const float eps = 0.00001f;
+  double div = 0.0;
+  int votes = 0;
+  for (int v = 0; v < reps; ++v) {
+    float x[kMaxClasses];
+    float s;
+    votes += (view_row_softmax(logits + inverse[(int64_t)v * p + i] * c, c, x, s) == arg) ? 1 : 0;
+    float term[kMaxClasses];
+#pragma unroll
+    for (int k = 0; k < kMaxClasses; ++k)
+      if (k < c) {
+        double a = (double)__fadd_rn(m[k], eps), b = (double)__fadd_rn(x[k] / s, eps);
+        // scipy.special.kl_div(a, b) = a log(a/b) - a + b  (a, b > 0 here), f32 result
+        term[k] = (float)(a * log(a / b) - a + b);
+      }
+    div += (double)np_sum_f32(term, c);
+  }
+  // scipy.stats.entropy(m), as interframe_kernel takes it of its mean row
+  float tot = np_sum_f32(m, c);
+  float ent[kMaxClasses];
+#pragma unroll
+  for (int k = 0; k < kMaxClasses; ++k)
+    if (k < c) {
+      float q = m[k] / tot;
+      ent[k] = (q > 0.f) ? (float)(-(double)q * log((double)q)) : 0.f;
+    }
+  viewe[i] = np_sum_f32(ent, c);
+  viewd[i] = div / (double)reps;
+  agree[i] = votes;
+}
+
 // ---------------- confusion matrix of evaluate.py:100-109 + utils/iou_sk.py:14-19 ----------------
 // per point: voxel row through the inverse index, argmax over the c logits (first maximum, as
 // torch.max / np.argmax), and conf[pred * c + gt] += 1 for labelled points (gt < 100).  Integer
@@ -378,6 +465,18 @@ extern "C" int lidal_view_mean_softmax(const float* logits, const int64_t* inver
   view_mean_softmax_kernel<<<(unsigned)cdiv(p, 256), 256, 0, (hipStream_t)stream>>>(
       logits, inverse, reps, p, c, prob, pred);
   LIDAL_CHECK_LAUNCH("lidal_view_mean_softmax");
+  return 0;
+}
+
+extern "C" int lidal_view_scores(const float* logits, const int64_t* inverse, int reps, int64_t p, int c,
+                                 float* prob, int64_t* pred, double* viewd, float* viewe, int32_t* agree,
+                                 void* stream) {
+  LIDAL_REQUIRE(c > 0 && c <= kMaxClasses, "view_scores: classes must be in 1..%d", kMaxClasses);
+  LIDAL_REQUIRE(reps > 0, "view_scores: reps must be positive");
+  if (p == 0) return 0;
+  view_scores_kernel<<<(unsigned)cdiv(p, 256), 256, 0, (hipStream_t)stream>>>(
+      logits, inverse, reps, p, c, prob, pred, viewd, viewe, agree);
+  LIDAL_CHECK_LAUNCH("lidal_view_scores");
   return 0;
 }
 

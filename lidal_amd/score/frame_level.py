@@ -9,6 +9,7 @@
   coreset             core_set.py:74-92, the greedy k-center over all frames' features (lidal_coreset)
   select_frames       the 1 % top-k of ENT / MAR / CONF / SEGENT (see reference_zero_half below)
   random_frames       frame_level/RAND.py's draw
+  VIEWD / VIEWE / VOTE  beyond the reference: how much the augmented views of a frame disagreed (view_level.py)
   frame_sequence      infer_frame per frame, then only the requested scores (scalars, or a [96] vector for CSET)
   FrameBoard          all sequences' frames in train_split order (the reference's seq_offsets), the per-sequence flags
 
@@ -25,8 +26,10 @@ from .. import io
 __all__ = ['frame_uncertainty', 'segment_entropy', 'frame_feature', 'coreset', 'num_to_add', 'select_frames',
            'random_frames', 'frame_sequence', 'FrameBoard', 'METRICS', 'SK_TRAIN_SPLIT']
 
-METRICS = ('ENT', 'MAR', 'CONF', 'SEGENT', 'CSET')
-LARGEST = {'ENT': True, 'MAR': True, 'CONF': False, 'SEGENT': True}       # MAR: "largest", as the reference (sic)
+METRICS = ('ENT', 'MAR', 'CONF', 'SEGENT', 'CSET', 'VIEWD', 'VIEWE', 'VOTE')
+LARGEST = {'ENT': True, 'MAR': True, 'CONF': False, 'SEGENT': True,       # MAR: "largest", as the reference (sic)
+           'VIEWD': True, 'VIEWE': True, 'VOTE': True}
+VIEW_METRICS = ('VIEWD', 'VIEWE', 'VOTE')
 SK_TRAIN_SPLIT = ['00', '01', '02', '03', '04', '05', '06', '07', '09', '10']
 MAX_CLASSES = 32
 MAX_FEAT_DIM = 128
@@ -197,17 +200,20 @@ def frame_sequence(model, frames, metrics=('ENT', 'MAR', 'CONF'), inf_reps=8, au
     """The scoring pass of the frame-level metrics over one sequence on one GPU: per frame infer_frame (with the [P, 96]
     feature only when CSET is asked), then only the requested values.  Frame dicts are score_sequence's (coords, feats,
     inverse; sv_ptr / sv_idx for SEGENT).  class_num (SEGENT) defaults to the model's class count.  Returns
-    {metric: [per frame: f32 0-d (ENT / MAR / CONF), f64 0-d (SEGENT) or f32 [D] (CSET) device tensor]}."""
+    {metric: [per frame: f32 0-d (ENT / MAR / CONF / VIEWD / VIEWE / VOTE), f64 0-d (SEGENT) or f32 [D] (CSET) device
+    tensor]}.  VIEWD / VIEWE / VOTE come out of the same inference (view_level.frame_view_scores)."""
     from .prob_inference import infer_frame
+    from .view_level import frame_view_scores
     metrics = tuple(metrics)
     bad = [m for m in metrics if m not in METRICS]
     if bad:
         raise ValueError('frame_sequence: unknown metrics %s (known: %s)' % (bad, METRICS))
     want_feat = 'CSET' in metrics
+    want_views = any(m in metrics for m in VIEW_METRICS)
     out = {m: [] for m in metrics}
     for d in frames:
         r = infer_frame(model, d['coords'], d['feats'], d['inverse'], inf_reps, autocast=autocast,
-                        return_feat=want_feat)
+                        return_feat=want_feat, return_view_scores=want_views)
         prob, pred = r[0], r[1]
         if any(m in metrics for m in ('ENT', 'MAR', 'CONF')):
             ent, mar, conf = frame_uncertainty(prob)
@@ -219,6 +225,10 @@ def frame_sequence(model, frames, metrics=('ENT', 'MAR', 'CONF'), inf_reps=8, au
                                                  prob.shape[1] if class_num is None else class_num))
         if want_feat:
             out['CSET'].append(frame_feature(r[2]))
+        if want_views:
+            for m, v in zip(VIEW_METRICS, frame_view_scores(*r[-1], inf_reps)):
+                if m in out:
+                    out[m].append(v)
     return out
 
 
