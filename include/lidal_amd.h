@@ -167,6 +167,47 @@ int lidal_train_labels(const void* raw, int raw_bytes, int64_t p, const int64_t*
                        const int64_t* pseudo, const int64_t* unique_idx, int64_t n, int64_t* labels_p,
                        int64_t* labels_v, int32_t* n_invalid_dev, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- mixed training samples: LaserMix / PolarMix style batches (csrc/mix.hip) ------------------ */
+/* The project's own definition; nothing in the reference does this.  The input is a list of
+ * scans laid end to end: xyz f32 [p_total,3], intensity f32 [p_total], labels i64 [p_total] or NULL.  A mix names two
+ * row ranges A and B of that list and, per point (every f32 operation rounded on its own, no fma),
+ *     r    = sqrtf(x*x + y*y)
+ *     band = #{ j < n_tans : z >= tans[j] * r }
+ *     inw  = has_wedge and wedge[0]*y - wedge[1]*x >= 0 and wedge[2]*y - wedge[3]*x < 0
+ *     cell = band + (n_tans + 1) * inw                                              (< 64)
+ * Its output rows are, in this order and inside each part in source order: the rows of A whose cell bit is set in
+ * take_a; the rows of B whose cell bit is set in take_b; and for each rotation k < n_rot the rows of B with a label in
+ * 0..63 whose bit is set in paste_classes, with x' = c*x - s*y, y' = s*x + c*y, z' = z, (c, s) = rot[2k], rot[2k+1]. */
+#define LIDAL_MIX_MAX 32          /* mixes in one call */
+#define LIDAL_MIX_MAX_TANS 31
+#define LIDAL_MIX_MAX_ROT 4
+#define LIDAL_MIX_PARTS 6         /* A, B and four pastes */
+typedef struct lidal_mix_desc {   /* 256 bytes */
+  int64_t a0, na, b0, nb;         /* A = rows a0 .. a0 + na of the input list, B = rows b0 .. b0 + nb (they may overlap) */
+  uint64_t take_a, take_b;        /* one bit per cell; no bit at or above (n_tans + 1) * (1 + has_wedge) */
+  uint64_t paste_classes;         /* one bit per class id 0..63 */
+  int32_t n_tans, has_wedge, n_rot, reserved;
+  float wedge[4];                 /* (d0x, d0y, d1x, d1y) */
+  float rot[2 * LIDAL_MIX_MAX_ROT];
+  float tans[LIDAL_MIX_MAX_TANS]; /* ascending, finite */
+  int32_t pad[3];
+} lidal_mix_desc;
+/*   mixes_host  n_mixes <= 32 descriptors in HOST memory; the call uploads them once (they must stay valid until the
+ *               stream has passed the call).  The slot space of mix m is na + nb * (1 + n_rot); n_slots is its sum over
+ *               the mixes and must be below 2^30.
+ *   out_xyz f32 [n_slots,3], out_intensity f32 [n_slots], out_labels i64 [n_slots] (NULL exactly when labels is; a
+ *   paste then is refused), out_src i64 [n_slots]: the input row each output row was taken from (the B row for a
+ *   paste).  Rows at and above point_ptr[n_mixes] are not written.
+ *   counts_dev i64 [n_mixes + 1 + 6 n_mixes]: point_ptr (mix m owns the output rows point_ptr[m] .. point_ptr[m+1])
+ *   followed by parts [n_mixes,6], the row counts of A, B and the four pastes.
+ * Three launches (per-block counts, their scan, the ordered write), no atomics, no memset.  Workspace:
+ * lidal_mix_scans_workspace_bytes(n_slots, n_mixes). */
+int64_t lidal_mix_scans_workspace_bytes(int64_t n_slots, int n_mixes);
+int lidal_mix_scans(const float* xyz, const float* intensity, const int64_t* labels, int64_t p_total,
+                    const lidal_mix_desc* mixes_host, int n_mixes, float* out_xyz, float* out_intensity,
+                    int64_t* out_labels, int64_t* out_src, int64_t* counts_dev, void* ws, int64_t ws_bytes,
+                    void* stream);
+
 /* ---- kernel map (rule) building -------------------------------------------------------------- */
 /* replaces the cache-miss branch of F.conv3d (torchsparse/nn/functional/conv.py): kernel_hash +
  * hash_query + nonzero.  `table` was built from sphash(in_coords).

@@ -53,6 +53,8 @@ SIGNATURES = {
     'lidal_train_labels_workspace_bytes': (_i64, [_i64]),
     'lidal_train_labels': (_i32, [_vp, _i32, _i64, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                   _vp, _i64, _vp]),
+    'lidal_mix_scans_workspace_bytes': (_i64, [_i64, _i32]),
+    'lidal_mix_scans': (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'lidal_kmap_workspace_bytes': (_i64, [_i64, _i32]),
     'lidal_kmap_build': (_i32, [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
                                 _i64, _vp]),

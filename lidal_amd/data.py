@@ -21,6 +21,11 @@ Whole batches: `voxelize_batch` voxelises and collates up
 the augmented views of one scan -- in lidal_voxelize_batch with one read-back; `train_batch`, `val_batch` and
 `score_sample` / `score_frame_inputs` compose it into the three __getitem__ + collate_fn modes of the reference, ending
 in what train_step, evaluate_batches and score_sequence take.
+
+Mixed batches (the project's own definition, nothing of the reference): `mix_scans` builds up to 32
+mixed samples -- inclination bands or an azimuth sector of two scans interleaved, rotated copies of the rows of chosen
+classes pasted -- in lidal_mix_scans with one read-back; `draw_lasermix` / `draw_polarmix` make the `Mix` records on the
+host and `mixed_train_batch` puts the step in front of voxelize_batch.
 """
 import math
 
@@ -33,7 +38,8 @@ __all__ = ['draw_augmentation', 'voxelize_scan', 'collate', 'parse_calibration',
            'register_scan', 'sk_label_map', 'nu_label_map', 'train_labels', 'train_sample', 'check_labels',
            'labeled_frames', 'frames_from_flag', 'kmeans_supervoxels', 'supervoxel_tables', 'balanced_assign',
            'supervoxel_bounds', 'supervoxel_costs', 'voxelize_batch', 'score_sample', 'val_batch', 'train_batch',
-           'score_frame_inputs', 'class_weights']
+           'score_frame_inputs', 'class_weights', 'Mix', 'identity_mix', 'wedge_vectors', 'class_mask', 'draw_lasermix',
+           'draw_polarmix', 'mix_scans', 'mixed_train_batch']
 
 SCALE = 20                # sk_dataset.py:56
 FULL_SCALE = 8192
@@ -395,6 +401,250 @@ def score_frame_inputs(points, intensity, pose, sv2point, inf_reps=8, rng=np.ran
     sv_ptr, sv_idx, _ = sv_csr(sv2point, points.device)
     return {'coords': batch['coords_v_b'], 'feats': batch['feats_v_b'], 'inverse': batch['inverse_indices_b'],
             'world': register_scan(points, pose), 'sv_ptr': sv_ptr, 'sv_idx': sv_idx}
+
+
+# ---- mixed training batches: LaserMix / PolarMix style (csrc/mix.hip) -------------------------
+MAX_MIXES = 32            # include/lidal_amd.h LIDAL_MIX_MAX
+MAX_MIX_TANS = 31
+MAX_MIX_ROT = 4
+MAX_MIX_SLOTS = 2 ** 30 - 1
+_MIX_DESC = np.dtype([('a0', '<i8'), ('na', '<i8'), ('b0', '<i8'), ('nb', '<i8'), ('take_a', '<u8'), ('take_b', '<u8'),
+                      ('paste_classes', '<u8'), ('n_tans', '<i4'), ('has_wedge', '<i4'), ('n_rot', '<i4'),
+                      ('reserved', '<i4'), ('wedge', '<f4', 4), ('rot', '<f4', 2 * MAX_MIX_ROT),
+                      ('tans', '<f4', MAX_MIX_TANS), ('pad', '<i4', 3)])          # lidal_mix_desc, 256 bytes
+_ALL_CELLS = 2 ** 64 - 1
+
+
+class Mix:
+    """One mixed sample of mix_scans.  Every float is an f32 value made on the host.
+      a, b            the two scans (indices into the call's lists; they may be equal)
+      tans            0..31 ascending finite tangents of the pitch boundaries: band = #{j : z >= tans[j] * r}
+      wedge           None, or (d0x, d0y, d1x, d1y): the sector from direction d0 (included) to d1 (excluded), of width
+                      in (0, pi] (wedge_vectors)
+      take_a, take_b  64-bit masks over the cells, cell = band + (len(tans) + 1) * in_sector
+      paste_classes   64-bit mask over the class ids 0..63 whose rows of B are pasted
+      paste_rot       0..4 pairs (cos, sin): one rotated copy of those rows each"""
+    __slots__ = ('a', 'b', 'tans', 'wedge', 'take_a', 'take_b', 'paste_classes', 'paste_rot')
+
+    def __init__(self, a, b, tans=(), wedge=None, take_a=0, take_b=0, paste_classes=0, paste_rot=()):
+        self.a, self.b = int(a), int(b)
+        self.tans = np.asarray(tans, dtype=np.float32).reshape(-1)
+        self.wedge = None if wedge is None else np.asarray(wedge, dtype=np.float32).reshape(-1)
+        self.take_a, self.take_b, self.paste_classes = int(take_a), int(take_b), int(paste_classes)
+        self.paste_rot = np.asarray(paste_rot, dtype=np.float32).reshape(-1, 2)
+
+    def __eq__(self, other):
+        return isinstance(other, Mix) and all(
+            np.array_equal(getattr(self, k), getattr(other, k)) if isinstance(getattr(self, k), np.ndarray)
+            else getattr(self, k) == getattr(other, k) for k in Mix.__slots__)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return 'Mix(%s)' % ', '.join('%s=%r' % (k, getattr(self, k)) for k in Mix.__slots__)
+
+
+def identity_mix(a):
+    """The mix that returns scan `a` unchanged: no boundaries, every cell of A, nothing else."""
+    return Mix(a, a, take_a=1)
+
+
+def wedge_vectors(alpha, width=math.pi):
+    """The f32 direction vectors (cos a, sin a, cos(a + w), sin(a + w)) of the sector [alpha, alpha + width), taken in
+    f64 and then cast; 0 < width <= pi."""
+    if not 0.0 < width <= math.pi:
+        raise ValueError('wedge_vectors: width=%r must be in (0, pi]' % (width,))
+    return np.array([math.cos(alpha), math.sin(alpha), math.cos(alpha + width), math.sin(alpha + width)],
+                    dtype=np.float64).astype(np.float32)
+
+
+def class_mask(classes):
+    """Class ids 0..63 -> the 64-bit mask of Mix.paste_classes."""
+    mask = 0
+    for c in classes:
+        if not 0 <= int(c) < 64:
+            raise ValueError('class_mask: class id %r is outside 0..63' % (c,))
+        mask |= 1 << int(c)
+    return mask
+
+
+def draw_lasermix(a, b, rng=np.random, areas=(3, 4, 5, 6), pitch_deg=(-25.0, 3.0)):
+    """Two twin mixes that interleave the inclination bands of scans a and b.  ONE draw: rng.randint(len(areas)) picks
+    the number of areas n.  The n - 1 boundaries are equally spaced in pitch strictly inside pitch_deg; their tangents
+    are taken in f64 and cast to f32.  Mix 1 takes A's even areas (0 = the lowest) and B's odd ones, the twin the
+    complement: together they hold every row of A and of B once."""
+    n = int(areas[int(rng.randint(len(areas)))])
+    if not 1 <= n <= MAX_MIX_TANS + 1:
+        raise ValueError('draw_lasermix: %d areas (1..%d)' % (n, MAX_MIX_TANS + 1))
+    lo, hi = float(pitch_deg[0]), float(pitch_deg[1])
+    pitch = lo + (hi - lo) * np.arange(1, n, dtype=np.float64) / n
+    tans = np.tan(np.deg2rad(pitch)).astype(np.float32)
+    even = sum(1 << c for c in range(0, n, 2))
+    odd = sum(1 << c for c in range(1, n, 2))
+    return Mix(a, b, tans, take_a=even, take_b=odd), Mix(a, b, tans, take_a=odd, take_b=even)
+
+
+def draw_polarmix(a, b, rng=np.random, paste_classes=(), n_rot=3):
+    """Two twin mixes that swap an azimuth sector of scans a and b.  Draws, in order: ONE rng.rand() u, alpha = 2 pi u,
+    the sector is [alpha, alpha + pi); then, only with paste_classes, n_rot further rng.rand() u_k, rotation k =
+    (k + u_k) * 2 pi / n_rot.  Mix 1 takes A outside the sector and B inside and pastes the rotated rows of B's
+    paste_classes; the twin is the same mix of (b, a): B outside, A inside, pastes from A.  Without paste the twins
+    hold every row of A and of B once."""
+    alpha = 2.0 * math.pi * float(rng.rand())
+    wedge = wedge_vectors(alpha, math.pi)
+    mask, rot = class_mask(paste_classes), []
+    if mask:
+        if not 0 <= int(n_rot) <= MAX_MIX_ROT:
+            raise ValueError('draw_polarmix: n_rot=%r (0..%d)' % (n_rot, MAX_MIX_ROT))
+        for k in range(int(n_rot)):
+            ang = (k + float(rng.rand())) * 2.0 * math.pi / int(n_rot)
+            rot.append((math.cos(ang), math.sin(ang)))
+    rot = np.array(rot, dtype=np.float64).astype(np.float32).reshape(-1, 2)
+    kw = dict(wedge=wedge, take_a=0b01, take_b=0b10, paste_classes=mask if len(rot) else 0, paste_rot=rot)
+    return Mix(a, b, **kw), Mix(b, a, **kw)
+
+
+def _mix_arguments(n_points, mixes, has_labels):
+    """The checks of mix_scans that need no device -> (descriptors as a _MIX_DESC array, slots, point_ptr of the
+    input).  Everything refused here raises ValueError."""
+    what = 'mix_scans'
+    mixes = list(mixes)
+    if not mixes:
+        raise ValueError('%s: no mixes' % what)
+    if len(mixes) > MAX_MIXES:
+        raise ValueError('%s: %d mixes in one call (at most %d)' % (what, len(mixes), MAX_MIXES))
+    s = len(n_points)
+    ptr = np.concatenate([[0], np.cumsum(n_points)]).astype(np.int64)
+    desc = np.zeros(len(mixes), dtype=_MIX_DESC)
+    slots = 0
+    for j, m in enumerate(mixes):
+        if not (0 <= m.a < s and 0 <= m.b < s):
+            raise ValueError('%s: mix %d: scans %d and %d of %d' % (what, j, m.a, m.b, s))
+        t = np.asarray(m.tans, dtype=np.float32).reshape(-1)
+        if len(t) > MAX_MIX_TANS:
+            raise ValueError('%s: mix %d: %d boundaries (at most %d)' % (what, j, len(t), MAX_MIX_TANS))
+        if not np.isfinite(t).all() or (np.diff(t) < 0).any():
+            raise ValueError('%s: mix %d: the boundaries must be finite and ascending' % (what, j))
+        w = None if m.wedge is None else np.asarray(m.wedge, dtype=np.float32).reshape(-1)
+        if w is not None and (w.shape != (4,) or not np.isfinite(w).all()):
+            raise ValueError('%s: mix %d: the sector takes four finite numbers (d0x, d0y, d1x, d1y)' % (what, j))
+        cells = (len(t) + 1) * (1 if w is None else 2)
+        for name in ('take_a', 'take_b', 'paste_classes'):
+            if not 0 <= getattr(m, name) <= _ALL_CELLS:
+                raise ValueError('%s: mix %d: %s is not a 64-bit mask' % (what, j, name))
+        if (m.take_a | m.take_b) >> cells:
+            raise ValueError('%s: mix %d: a mask bit at or above the %d cells' % (what, j, cells))
+        rot = np.asarray(m.paste_rot, dtype=np.float32).reshape(-1, 2)
+        if len(rot) > MAX_MIX_ROT:
+            raise ValueError('%s: mix %d: %d rotations (at most %d)' % (what, j, len(rot), MAX_MIX_ROT))
+        if not np.isfinite(rot).all():
+            raise ValueError('%s: mix %d: the rotations must be finite' % (what, j))
+        if len(rot) and not has_labels:
+            raise ValueError('%s: mix %d: a paste needs labels' % (what, j))
+        d = desc[j]
+        d['a0'], d['na'], d['b0'], d['nb'] = ptr[m.a], n_points[m.a], ptr[m.b], n_points[m.b]
+        d['take_a'], d['take_b'], d['paste_classes'] = m.take_a, m.take_b, m.paste_classes
+        d['n_tans'], d['has_wedge'], d['n_rot'] = len(t), w is not None, len(rot)
+        d['tans'][:len(t)] = t
+        if w is not None:
+            d['wedge'][:] = w
+        d['rot'][:2 * len(rot)] = rot.reshape(-1)
+        slots += int(n_points[m.a]) + int(n_points[m.b]) * (1 + len(rot))
+        if slots > MAX_MIX_SLOTS:
+            raise ValueError('%s: %d slots in one call (fewer than 2^30)' % (what, slots))
+    return desc, slots, ptr
+
+
+def mix_scans(points, intensity, labels, mixes):
+    """M = len(mixes) mixed samples from S scans in ONE library call (lidal_mix_scans: three launches, no atomics) with
+    one read-back.
+      points / intensity   lists of S GPU tensors f32 [P_s,3] / [P_s], as voxelize_batch takes them
+      labels               list of S i64 [P_s] (the labels_p of train_labels; 255 = ignored), or None: then no label
+                           output and no paste
+      mixes                1..32 Mix records
+    Returns {'points' f32 [N,3], 'intensity' f32 [N], 'labels' i64 [N] or None, 'src' i64 [N]} on the device -- the
+    samples laid end to end; src is the row of the concatenated input list each row was taken from (the B row for a
+    paste), so any other per-point array follows with array[src] -- and on the host 'point_ptr' i64 [M+1] (sample m owns
+    rows point_ptr[m]:point_ptr[m+1]) and 'parts' i64 [M,6], the row counts of A, B and the four pastes.  The outputs are
+    allocated at the slot bound sum(n_a + n_b (1 + rotations)) and returned as slices.  ValueError, before anything
+    touches the device, for no mixes or more than 32, a scan index out of range, more than 31 boundaries or boundaries
+    that are not finite and ascending, a sector that is not finite, mask bits at or above the cell count, more than 4
+    rotations, a paste without labels and 2^30 or more slots."""
+    what = 'mix_scans'
+    pts, inten = list(points), list(intensity)
+    labs = None if labels is None else list(labels)
+    if len(inten) != len(pts) or (labs is not None and len(labs) != len(pts)):
+        raise ValueError('%s: %d point tensors, %d intensity tensors and %s label tensors'
+                         % (what, len(pts), len(inten), 'no' if labs is None else len(labs)))
+    for j, x in enumerate(pts):
+        if not torch.is_tensor(x) or x.ndim != 2 or x.shape[1] != 3:
+            raise ValueError('%s: scan %d: points must be [P, 3], not %s' % (what, j, tuple(getattr(x, 'shape', ()))))
+        for name, other in (('intensities', inten), ('labels', labs)):
+            if other is not None and (not torch.is_tensor(other[j]) or other[j].numel() != x.shape[0]):
+                raise ValueError('%s: scan %d: %d %s for %d points'
+                                 % (what, j, other[j].numel() if torch.is_tensor(other[j]) else -1, name, x.shape[0]))
+    desc, slots, _ = _mix_arguments([x.shape[0] for x in pts], mixes, labs is not None)
+    m = len(desc)
+    B.require_gpu(*pts, *inten, *(labs or []))
+    pts = [x.contiguous().float() for x in pts]
+    inten = [w.contiguous().float().reshape(-1) for w in inten]
+    xyz = pts[0] if len(pts) == 1 else torch.cat(pts)
+    w_all = inten[0] if len(inten) == 1 else torch.cat(inten)
+    lab_all = None
+    if labs is not None:
+        labs = [l.to(torch.int64).contiguous().reshape(-1) for l in labs]
+        lab_all = labs[0] if len(labs) == 1 else torch.cat(labs)
+    dev = xyz.device
+    cap = max(slots, 1)
+    out_xyz = B.empty((cap, 3), torch.float32, dev)
+    out_w = B.empty(cap, torch.float32, dev)
+    out_lab = B.empty(cap, torch.int64, dev) if lab_all is not None else None
+    out_src = B.empty(cap, torch.int64, dev)
+    counts = torch.empty(m + 1 + 6 * m, dtype=torch.int64, device=dev)               # point_ptr [M+1] | parts [M,6]
+    ws_bytes = B.lib().lidal_mix_scans_workspace_bytes(slots, m)
+    ws = B.workspace(ws_bytes, dev)
+    B.check(B.lib().lidal_mix_scans(B.ptr(xyz), B.ptr(w_all), B.ptr(lab_all), xyz.shape[0], desc.ctypes.data, m,
+                                    B.ptr(out_xyz), B.ptr(out_w), B.ptr(out_lab), B.ptr(out_src), B.ptr(counts),
+                                    B.ptr(ws), ws_bytes, B.stream()), 'mix_scans')
+    host = counts.cpu().numpy()                                                       # the one read-back
+    point_ptr, parts = host[:m + 1].copy(), host[m + 1:].reshape(m, 6).copy()
+    n = int(point_ptr[-1])
+    return {'points': out_xyz[:n], 'intensity': out_w[:n], 'labels': out_lab[:n] if out_lab is not None else None,
+            'src': out_src[:n], 'point_ptr': point_ptr, 'parts': parts}
+
+
+def mixed_train_batch(scans, raw_labels, label_map, mixes, sv_csrs=None, sv_flags=None, pseudos=None, rng=np.random,
+                      check=True):
+    """train_batch over mixed samples: scans, raw_labels, sv_csrs, sv_flags and pseudos as train_batch takes them, and
+    one Mix per sample of the batch.  train_labels per scan (no read-back), mix_scans of the scans and their labels_p,
+    ONE draw_augmentation(rng) per mix in order, voxelize_batch over the mixed samples, labels_v_b = the mixed
+    labels[unique_idxs_b], one check_labels (check=False: the counters stay in 'labels_invalid') -> the batch of
+    train_step.  Beside it: labels_p_b and src_p_b per mixed point, src_b per voxel (rows of the concatenated input list:
+    any per-point array of the scans follows the batch with array[src]) and parts of mix_scans.  Two read-backs: the
+    mix's row counts and the batch's voxel counts.  identity_mix(j) for every scan gives train_batch's batch."""
+    if (sv_csrs is None) != (sv_flags is None):
+        raise ValueError('mixed_train_batch: sv_csrs and sv_flags come together')
+    scans = _batch_scans(scans, [('label arrays', raw_labels), ('supervoxel lists', sv_csrs), ('flag arrays', sv_flags),
+                                 ('pseudo label arrays', pseudos)], 'mixed_train_batch')
+    mixes = list(mixes)
+    _mix_arguments([x.shape[0] for x, _ in scans], mixes, True)         # refused before anything is launched
+    out = [train_labels(raw_labels[j], label_map, sv_csrs[j] if sv_csrs is not None else None,
+                        sv_flags[j] if sv_flags is not None else None, pseudos[j] if pseudos is not None else None,
+                        check=False) for j in range(len(scans))]
+    mixed = mix_scans([x for x, _ in scans], [w for _, w in scans], [o[0] for o in out], mixes)
+    draws = [draw_augmentation(rng) for _ in mixes]
+    ptr = mixed['point_ptr']
+    cut = [(int(ptr[j]), int(ptr[j + 1])) for j in range(len(mixes))]
+    batch = voxelize_batch([mixed['points'][a:b] for a, b in cut], [mixed['intensity'][a:b] for a, b in cut],
+                           [d[0] for d in draws], [d[1] for d in draws])
+    batch['labels_p_b'], batch['src_p_b'], batch['parts'] = mixed['labels'], mixed['src'], mixed['parts']
+    batch['labels_v_b'] = mixed['labels'][batch['unique_idxs_b']]
+    batch['src_b'] = mixed['src'][batch['unique_idxs_b']]
+    if check:
+        check_labels([o[2] for o in out])
+    else:
+        batch['labels_invalid'] = [o[2] for o in out]
+    return batch
 
 
 def class_weights(labels_v_b, n_classes, ignore=255, kind='inverse'):
