@@ -307,6 +307,11 @@ int64_t lidal_invlist_workspace_bytes(int64_t n_entries);
 int lidal_invlist_build(const int32_t* idx, const float* w, int64_t n_entries, int64_t m,
                         int32_t* order, int64_t* seg_ptr, void* ws, int64_t ws_bytes, void* stream);
 int64_t lidal_segment_workspace_bytes(int64_t n_entries, int64_t m, int c);
+/* Which kernel the two ordered sums below launch for these arguments (the choice follows the average list length
+ * n_entries / m, the voxel count, the row width and the element type -- never the lists themselves): 0 a lane group per
+ * voxel, 1 one wave per voxel, 11 / 12 / 14 a workgroup kernel with 1 / 2 / 4 workgroups per voxel (12 and 14 through f32
+ * partial rows in ws and a fold); -1 what they do not take.  A query: nothing is launched. */
+int64_t lidal_segment_form(int64_t n_entries, int64_t m, int c, int dtype);
 int lidal_voxelize_fwd_sorted(const void* feat, const int32_t* order, const int64_t* seg_ptr,
                               const int32_t* counts, void* out, int64_t m, int c, int dtype,
                               int64_t n_entries, void* ws, int64_t ws_bytes, void* stream);

@@ -71,6 +71,7 @@ SIGNATURES = {
     'lidal_invlist_workspace_bytes': (_i64, [_i64]),
     'lidal_invlist_build': (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     'lidal_segment_workspace_bytes': (_i64, [_i64, _i64, _i32]),
+    'lidal_segment_form': (_i64, [_i64, _i64, _i32, _i32]),
     'lidal_voxelize_fwd_sorted': (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _i64, _vp]),
     'lidal_devoxelize_bwd_sorted': (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _i64, _vp]),
     'lidal_devoxelize_bwd_cells': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),

@@ -102,13 +102,10 @@ __global__ void __launch_bounds__(256) voxelize_fwd_kernel(const float* __restri
   float div = (float)cnt;
   const float* src = feat + i * c + j;
   float* dst = out + (int64_t)pos * c + j;
-  if (cnt == 1) {          // sole contributor: plain store, no atomic
+  // (always a sum: `counts` is the divisor the caller hands in, not a promise about the number of contributors -- a
+  //  plain store for counts[pos] == 1 kept only the last of several points of such a voxel)
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) dst[v] = src[v] / div;
-  } else {
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) atomicAdd(&dst[v], src[v] / div);
-  }
+  for (int v = 0; v < VEC; ++v) atomicAdd(&dst[v], src[v] / div);
 }
 
 // gin[i] = gout[idx[i]] / counts[idx[i]]  (+ res[i]: the gradient that reaches the same point rows
@@ -541,6 +538,18 @@ static inline int segment_parts(int64_t n_entries, int64_t m, int c, int esz) {
 // (105 363 voxels, <= 30 entries) 62 against the wave kernel's 89.
 constexpr int64_t GROUP_MAX_AVG = 32, GROUP_MAX_AVG_FEW = 12, GROUP_MANY_VOXELS = 65536;
 
+// THE choice of the form of an ordered sum over m lists of n_entries / m entries on average (rows of c elements of esz
+// bytes) -- the launch, the scratch size and the query lidal_segment_form all ask here: 0 the lane-group kernel, 1 one wave
+// per voxel, 10 + parts the workgroup kernel with 1, 2 or 4 workgroups per voxel (more than one: an f32 partial row each
+// and the fold); -1 what the ordered sums do not take (no voxels, channels no multiple of 4 or more than 64 lanes hold).
+static inline int segment_form(int64_t n_entries, int64_t m, int c, int esz) {
+  if (m <= 0 || c <= 0 || c % 4 != 0 || c > 64 * segment_vec(c, esz)) return -1;
+  if (n_entries / m <= (m >= GROUP_MANY_VOXELS ? GROUP_MAX_AVG : GROUP_MAX_AVG_FEW)) return 0;
+  const int parts = segment_parts(n_entries, m, c, esz);
+  return parts == 0 ? 1 : 10 + parts;
+}
+static inline int segment_form_parts(int form) { return form > 10 ? form - 10 : 0; }
+
 template <typename T, int VEC, bool DEVOX>
 void launch_group(const T* src, const int* order, const int64_t* seg_ptr, const float* w, const int* counts,
                   T* out, int64_t m, int c, hipStream_t s) {
@@ -563,13 +572,15 @@ int launch_segment_sum(const T* src, const int* order, const int64_t* seg_ptr, c
   // a row is covered by at most 64 lanes of VEC channels each
   LIDAL_REQUIRE(c <= 64 * segment_vec(c, (int)sizeof(T)), "segment_sum: at most %d channels per row for this element type",
                 64 * segment_vec(c, (int)sizeof(T)));
-  if (m > 0 && n_entries / m <= (m >= GROUP_MANY_VOXELS ? GROUP_MAX_AVG : GROUP_MAX_AVG_FEW)) {
+  const int form = segment_form(n_entries, m, c, (int)sizeof(T));
+  LIDAL_REQUIRE(form >= 0, "segment_sum: nothing to launch for %lld voxels of %d channels", (long long)m, c);
+  if (form == 0) {
     if (sizeof(T) == 2 && c % 8 == 0) launch_group<T, 8, DEVOX>(src, order, seg_ptr, w, counts, out, m, c, s);
     else launch_group<T, 4, DEVOX>(src, order, seg_ptr, w, counts, out, m, c, s);
     LIDAL_CHECK_LAUNCH("segment_sum_group");
     return 0;
   }
-  const int parts = segment_parts(n_entries, m, c, (int)sizeof(T));
+  const int parts = segment_form_parts(form);
   float* partial = (float*)ws;
   if (parts > 1)
     LIDAL_REQUIRE(ws != nullptr && ws_bytes >= (int64_t)m * parts * c * 4, "segment_sum workspace too small");
@@ -915,9 +926,16 @@ extern "C" int lidal_invlist_build(const int32_t* idx, const float* w, int64_t n
 
 extern "C" int64_t lidal_segment_workspace_bytes(int64_t n_entries, int64_t m, int c) {
   // (f32 rows never need less than bf16 rows: the split is chosen per element size, the larger one is reported)
-  int parts = segment_parts(n_entries, m, c, 2), parts4 = segment_parts(n_entries, m, c, 4);
+  int parts = segment_form_parts(segment_form(n_entries, m, c, 2));
+  const int parts4 = segment_form_parts(segment_form(n_entries, m, c, 4));
   if (parts4 > parts) parts = parts4;
   return parts > 1 ? (int64_t)m * parts * c * 4 : 0;
+}
+
+// which kernel lidal_voxelize_fwd_sorted / lidal_devoxelize_bwd_sorted launch for these arguments (segment_form)
+extern "C" int64_t lidal_segment_form(int64_t n_entries, int64_t m, int c, int dtype) {
+  if (dtype != LIDAL_F32 && dtype != LIDAL_BF16) return -1;
+  return segment_form(n_entries, m, c, dtype == LIDAL_F32 ? 4 : 2);
 }
 
 extern "C" int lidal_voxelize_fwd_sorted(const void* feat, const int32_t* order,
