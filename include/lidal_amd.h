@@ -889,6 +889,49 @@ int lidal_adam_step(const void* table, int rec_begin, int rec_end, int64_t v_beg
                     float* m, float* v, int64_t state_numel, double one_minus_beta1, double beta2, double one_minus_beta2,
                     double bias_correction2_sqrt, double eps, double neg_step_size, double weight_decay, void* stream);
 
+/* ---- the mean-teacher step (csrc/semi.hip; not plan operations: all of it is the caller's loop) ------------ */
+/* The teacher as an exponential moving average of the student over any number of tensors in ONE launch, no
+ * synchronisation, nothing read back.  `table` (device): records of five 64-bit words, one per tensor --
+ *     { address of the teacher's tensor,  address of the student's,  vstart,  n 32-bit words,  kind }
+ * kind 0: t = t + (s - t) * (float)one_minus_alpha per f32 element, the two operations rounded separately (subnormals
+ * kept, NaN / Inf as IEEE says);  kind 1: the words are copied, no arithmetic touches them (an int64 is two words).
+ * all_copy != 0 treats every record as kind 1 (alpha == 0: t + (s - t) is not s in floating point).
+ * vstart places the tensor on a virtual axis of words that the kernel cuts into chunks of lidal_ema_chunk_elems()
+ * (ascending with the record index, ranges disjoint, gaps allowed, the first at or above 0, the last ending at or
+ * below v_end); 16-byte accesses wherever the two addresses share one 16-byte phase, 4-byte accesses otherwise and for
+ * the up to three words before / after the whole vectors.  Records with n <= 0 are skipped. */
+int lidal_ema_chunk_elems(void);
+int lidal_ema_step(const void* table, int n_recs, int64_t v_end, double one_minus_alpha, int all_copy, void* stream);
+/* Pseudo labels from a teacher's logits [nv, c] (dtype LIDAL_F32 / LIDAL_BF16, c in 1..32), one launch behind a memset
+ * of `stats`.  Per point i < p: its row is inverse[i] (inverse NULL: row i, and p == nv); arg = the first maximum of the
+ * row, conf = expf(x_arg - mx) / sum_k expf(x_k - mx), the f32 sum in class order.
+ *     out[i] = labels[i]                  where labels != NULL and labels[i] != ignore_index (in none of the counts)
+ *            = ignore_index               where the row is outside [0, nv): counted in stats[c + 1], never read through
+ *            = arg                        where conf >= thresholds[arg] (thresholds NULL: >= (float)threshold): stats[arg]
+ *            = ignore_index               otherwise (a row with a NaN always: the comparison is false): stats[c]
+ * out i64 [p], stats i64 [c + 2], conf f32 [p] or NULL (0 where the row is outside). */
+int lidal_pseudo_labels(const void* logits, int dtype, int64_t nv, int c, const float* thresholds, double threshold,
+                        const int64_t* inverse, const int64_t* labels, int64_t ignore_index, int64_t p, int64_t* out,
+                        int64_t* stats, float* conf, void* stream);
+/* Consistency between a student's and a teacher's rows [n, c] (each LIDAL_F32 or LIDAL_BF16 logits; is_probs = 1: f32
+ * probabilities, kind 0 only), c in 1..32, 0 < n, n * c < 2^30.  Both softmaxes are the f32 row softmax above;
+ * m_i = [teacher conf_i >= (float)min_conf]; r_i = np_sum_f32 over the classes of
+ *     kind 0 'mse':  fl(d_k * d_k), d_k = fl(ps_k - pt_k);                              denom = n * c
+ *     kind 1 'kl' :  pt_k * (lt_k - ls_k), 0 where pt_k == 0, l_k = (z_k - mx) - logf(s);   denom = n
+ * out2 f64 [2] = { sum_i m_i r_i / denom, sum_i m_i r_i }: f64 partials per workgroup of 256 rows, then one workgroup, a
+ * fixed order.  per_row f32 [n] or NULL: m_i r_i.  Two launches; workspace lidal_consistency_workspace_bytes(n).
+ * Backward (one launch), g = grad_scale[0] read on the device, dz in the student's dtype, 0 where m_i == 0:
+ *     'mse' on logits:        dz_k = (g * (float)(1 / (n c))) * (ps_k * (2 d_k - sum_j ps_j * (2 d_j))), j ascending in f32
+ *     'mse' on probabilities: dz_k = (g * (float)(2 / (n c))) * d_k
+ *     'kl':                   dz_k = (g * (float)(1 / n)) * (ps_k - pt_k)
+ * every product and difference one f32 operation, the constants formed in double. */
+int64_t lidal_consistency_workspace_bytes(int64_t n);
+int lidal_consistency_fwd(const void* student, int s_dtype, const void* teacher, int t_dtype, int64_t n, int c, int kind,
+                          int is_probs, double min_conf, double* out2, float* per_row, void* ws, int64_t ws_bytes,
+                          void* stream);
+int lidal_consistency_bwd(const void* student, int s_dtype, const void* teacher, int t_dtype, int64_t n, int c, int kind,
+                          int is_probs, double min_conf, const float* grad_scale, void* dz, void* stream);
+
 /* ---- launch plans ----------------------------------------------------------------------------------- */
 /* A whole forward or backward pass as ONE call: `words` is a stream of n_ops operations,
  *     kind | flags << 16,  arg 0, arg 1, ...

@@ -13,7 +13,7 @@ import sys
 from .operators import cat
 from .tensor import PointTensor, SparseTensor
 
-__all__ = ['SparseTensor', 'PointTensor', 'cat', 'install_as_torchsparse', 'adopt_torch_modules']
+__all__ = ['SparseTensor', 'PointTensor', 'cat', 'install_as_torchsparse', 'adopt_torch_modules', 'semi']
 __version__ = '0.1.0'
 
 
@@ -137,3 +137,6 @@ def adopt_torch_modules(model):
                 setattr(parent, name, seq)
     convert(model)
     return model
+
+
+from . import semi      # noqa: E402  (the mean-teacher step: EmaTeacher, pseudo_labels, consistency_loss, semi_train_step)

@@ -188,6 +188,12 @@ SIGNATURES = {
     'lidal_cast_rows_bf16': (_i32, [_vp, _i32, _vp, _i32, _i64, _vp]),
     'lidal_adam_chunk_elems': (_i32, []),
     'lidal_adam_step': (_i32, [_vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _vp]),
+    'lidal_ema_chunk_elems': (_i32, []),
+    'lidal_ema_step': (_i32, [_vp, _i32, _i64, _f64, _i32, _vp]),
+    'lidal_pseudo_labels': (_i32, [_vp, _i32, _i64, _i32, _vp, _f64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'lidal_consistency_workspace_bytes': (_i64, [_i64]),
+    'lidal_consistency_fwd': (_i32, [_vp, _i32, _vp, _i32, _i64, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _i64, _vp]),
+    'lidal_consistency_bwd': (_i32, [_vp, _i32, _vp, _i32, _i64, _i32, _i32, _i32, _f64, _vp, _vp, _vp]),
     'lidal_plan_op_args': (_i32, [_i32]),
     'lidal_debug_read': (_i32, [_vp, _vp, _i64]),
     'lidal_plan_run': (_i32, [_vp, _i64, _i64, _vp, _vp]),

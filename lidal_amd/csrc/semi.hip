@@ -1,0 +1,528 @@
+// The mean-teacher step of semi-supervised training (Tarvainen & Valpola 2017; what LaserMix / PolarMix train with):
+//   * lidal_ema_step          teacher = EMA of the student over EVERY parameter and buffer, in ONE launch;
+//   * lidal_pseudo_labels     the teacher's confident predictions as labels of the points nobody annotated, one launch;
+//   * lidal_consistency_fwd   the consistency term between student and teacher, 'mse' of the two softmaxes (mean teacher,
+//     lidal_consistency_bwd   LaserMix) or 'kl' (distillation), and its gradient with respect to the student.
+// The definitions are this project's own; tests/semi_ref.py restates them in numpy.  Built without fma contraction and
+// without packed-f32 instructions (lidal_amd/build.py); vector stores only, no float atomics: every float sum has one
+// fixed order, so two runs give the same bits.
+//
+// The row softmax everywhere is view_row_softmax of score.hip, restated for f32 and bf16 rows: first maximum,
+// expf(x - mx), running f32 sum in class order, f32 divide.
+#include "common.h"
+#include "npsum.h"
+
+#pragma clang fp contract(off)
+
+namespace lidal {
+namespace {
+
+using npsum::kMaxClasses;
+using npsum::np_sum_f32;
+
+// ---------------------------------------------------------------------------------------------------------- EMA
+// t = t + (s - t) * oma per f32 element (kind 0), or a copy of 32-bit words with no arithmetic on them (kind 1).  The
+// layout of the work is adam_step_kernel's (optim.hip): one record per tensor on a virtual axis of 32-bit words, cut into
+// chunks; a workgroup takes a run of chunks.  vstart = (teacher address / 4) mod 32 makes chunk boundaries 128-byte
+// boundaries of the large tensors; where teacher and student share a 16-byte phase a piece moves as 16-byte accesses
+// (a whole chunk: all loads before the first use), otherwise -- and for the up to three words before / after the whole
+// vectors -- as 4-byte accesses.
+constexpr int kEmaThreads = 256;
+constexpr int kEmaVecs = 4;
+constexpr int kEmaChunk = kEmaThreads * kEmaVecs * 4;       // 32-bit words
+constexpr int kEmaBlocksPerCU = 4;
+
+struct EmaRec {             // five 64-bit words: the table's record
+  uint64_t t;               // address of the teacher's tensor
+  uint64_t s;               // address of the student's
+  int64_t vstart;           // first word on the virtual axis (ascending with the record index, no overlap)
+  int64_t n;                // 32-bit words (an int64 element is two)
+  int64_t kind;             // 0: lerp (f32), 1: copy
+};
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LIDAL_GLOBAL __attribute__((address_space(1)))
+#else
+#define LIDAL_GLOBAL
+#endif
+typedef LIDAL_GLOBAL unsigned gword;
+typedef LIDAL_GLOBAL const unsigned cgword;
+typedef LIDAL_GLOBAL u32x4 gword4;
+typedef LIDAL_GLOBAL const u32x4 cgword4;
+
+__device__ __forceinline__ unsigned ema_word(unsigned t, unsigned s, float oma) {
+  const float tf = __uint_as_float(t), sf = __uint_as_float(s);
+  return __float_as_uint(tf + (sf - tf) * oma);
+}
+
+__device__ __forceinline__ u32x4 ema_vec(const u32x4& t, const u32x4& s, float oma) {
+  u32x4 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) r[e] = ema_word(t[e], s[e], oma);
+  return r;
+}
+
+// words [a, b) of one tensor (b - a <= kEmaChunk), by the whole workgroup
+template <bool COPY>
+__device__ __forceinline__ void ema_piece(gword* t, cgword* s, int64_t a, int64_t b, float oma) {
+  const int tid = threadIdx.x;
+  const uintptr_t ta = (uintptr_t)(t + a);
+  if (((ta ^ (uintptr_t)(s + a)) & 15) != 0) {
+    for (int64_t i = a + tid; i < b; i += kEmaThreads) t[i] = COPY ? s[i] : ema_word(t[i], s[i], oma);
+    return;
+  }
+  int64_t head = (int64_t)(((16 - (ta & 15)) & 15) >> 2);         // words before the first 16-byte boundary
+  if (head > b - a) head = b - a;
+  const int64_t v0 = a + head;
+  const int64_t nvec = (b - v0) >> 2;
+  const int64_t tail = v0 + nvec * 4;
+  gword4* t4 = (gword4*)(t + v0);
+  cgword4* s4 = (cgword4*)(s + v0);
+  if (nvec == kEmaThreads * kEmaVecs) {                           // a whole chunk: every load before the first use
+    u32x4 tt[kEmaVecs], ss[kEmaVecs];
+#pragma unroll
+    for (int j = 0; j < kEmaVecs; ++j) {
+      const int i = tid + j * kEmaThreads;
+      ss[j] = s4[i];
+      if (!COPY) tt[j] = t4[i];
+    }
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < kEmaVecs; ++j) t4[tid + j * kEmaThreads] = COPY ? ss[j] : ema_vec(tt[j], ss[j], oma);
+  } else {
+    for (int64_t i = tid; i < nvec; i += kEmaThreads) {
+      const u32x4 ss = s4[i];
+      t4[i] = COPY ? ss : ema_vec(t4[i], ss, oma);
+    }
+  }
+  if (tid < head) t[a + tid] = COPY ? s[a + tid] : ema_word(t[a + tid], s[a + tid], oma);
+  if (tid < b - tail) t[tail + tid] = COPY ? s[tail + tid] : ema_word(t[tail + tid], s[tail + tid], oma);
+}
+
+__global__ __launch_bounds__(kEmaThreads) void ema_step_kernel(const EmaRec* __restrict__ recs, int n_recs,
+                                                               int64_t n_chunks, float oma, int all_copy) {
+  const int64_t c0 = n_chunks * (int64_t)blockIdx.x / gridDim.x, c1 = n_chunks * ((int64_t)blockIdx.x + 1) / gridDim.x;
+  if (c0 >= c1) return;
+  // first record that ends behind the start of chunk c0 (all of this is uniform over the workgroup)
+  const int64_t first = c0 * kEmaChunk;
+  int lo = 0, hi = n_recs;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (recs[mid].vstart + recs[mid].n <= first) lo = mid + 1; else hi = mid;
+  }
+  int r = lo;
+  for (int64_t c = c0; c < c1; ++c) {
+    const int64_t cs = c * kEmaChunk, ce = cs + kEmaChunk;
+    while (r < n_recs && recs[r].vstart + recs[r].n <= cs) ++r;
+    for (int q = r; q < n_recs; ++q) {
+      const EmaRec R = recs[q];
+      if (R.vstart >= ce) break;
+      if (R.n <= 0) continue;
+      const int64_t a = (cs > R.vstart ? cs : R.vstart) - R.vstart;
+      const int64_t e = (ce < R.vstart + R.n ? ce : R.vstart + R.n) - R.vstart;
+      if (all_copy || R.kind != 0)
+        ema_piece<true>((gword*)R.t, (cgword*)R.s, a, e, oma);
+      else
+        ema_piece<false>((gword*)R.t, (cgword*)R.s, a, e, oma);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------- rows
+template <typename T>
+__device__ __forceinline__ int row_softmax(const T* __restrict__ row, int c, float (&x)[kMaxClasses], float& mx, float& s) {
+  mx = -INFINITY;
+  int arg = 0;
+#pragma unroll
+  for (int j = 0; j < kMaxClasses; ++j)
+    if (j < c) {
+      x[j] = (float)row[j];
+      if (x[j] > mx) arg = j;
+      mx = fmaxf(mx, x[j]);
+    }
+  s = 0.f;
+#pragma unroll
+  for (int j = 0; j < kMaxClasses; ++j)
+    if (j < c) { x[j] = expf(x[j] - mx); s += x[j]; }
+  return arg;
+}
+
+// the value of x[arg] for a run-time arg, without indexing the register array
+__device__ __forceinline__ float pick(const float (&x)[kMaxClasses], int c, int arg) {
+  float v = 0.f;
+#pragma unroll
+  for (int j = 0; j < kMaxClasses; ++j)
+    if (j < c && j == arg) v = x[j];
+  return v;
+}
+
+// ---------------------------------------------------------------------------------------------------------- pseudo labels
+constexpr int PL_THREADS = 256;
+
+template <typename T>
+__global__ void __launch_bounds__(PL_THREADS) pseudo_labels_kernel(const T* __restrict__ logits, int64_t nv, int c,
+                                                                   const float* __restrict__ thresholds, float threshold,
+                                                                   const int64_t* __restrict__ inverse,
+                                                                   const int64_t* __restrict__ labels,
+                                                                   int64_t ignore_index, int64_t p,
+                                                                   int64_t* __restrict__ out,
+                                                                   unsigned long long* __restrict__ stats,
+                                                                   float* __restrict__ conf_out) {
+  __shared__ int cnt[kMaxClasses + 2];
+  if (threadIdx.x < kMaxClasses + 2) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * PL_THREADS + threadIdx.x;
+  if (i < p) {
+    const int64_t row = inverse != nullptr ? inverse[i] : i;
+    const bool in = row >= 0 && row < nv;                 // a bad index is never read through
+    const int64_t human = labels != nullptr ? labels[i] : ignore_index;
+    int arg = 0;
+    float conf = 0.f;
+    if (in) {
+      float x[kMaxClasses], mx, s;
+      arg = row_softmax<T>(logits + row * c, c, x, mx, s);
+      conf = pick(x, c, arg) / s;
+    }
+    int64_t y = ignore_index;
+    int slot = -1;
+    if (human != ignore_index) {
+      y = human;                                          // (in none of the counts)
+    } else if (!in) {
+      slot = c + 1;
+    } else {
+      const float thr = thresholds != nullptr ? thresholds[arg] : threshold;
+      if (conf >= thr) { y = arg; slot = arg; } else slot = c;        // (a NaN compares false: rejected)
+    }
+    out[i] = y;
+    if (conf_out != nullptr) conf_out[i] = conf;
+    if (slot >= 0) atomicAdd(&cnt[slot], 1);
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < c + 2 && cnt[threadIdx.x] != 0)
+    atomicAdd(&stats[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
+}
+
+// ---------------------------------------------------------------------------------------------------------- consistency
+constexpr int CS_ROWS = 256;
+enum { KIND_MSE = 0, KIND_KL = 1 };
+
+// A workgroup's rows are one contiguous piece of the [n, c] matrix: moved with whole-wave contiguous accesses whatever
+// c is, through an LDS image whose rows are c | 1 words apart (lanes reading their own row do not meet in one bank).
+template <typename T>
+__device__ __forceinline__ void rows_in(const T* __restrict__ src, int64_t row0, int rows, int c, int cs,
+                                        float* __restrict__ lds) {
+  const T* p = src + row0 * c;
+  const int total = rows * c;
+  const int dr = CS_ROWS / c, dc = CS_ROWS % c;         // (row, column) of element q + 256 from those of q: no division per element
+  int r = threadIdx.x / c, k = threadIdx.x % c;
+  for (int q = threadIdx.x; q < total; q += CS_ROWS) {
+    lds[r * cs + k] = (float)p[q];
+    r += dr; k += dc;
+    if (k >= c) { k -= c; ++r; }
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void rows_out(T* __restrict__ dst, int64_t row0, int rows, int c, int cs,
+                                         const float* __restrict__ lds) {
+  T* p = dst + row0 * c;
+  const int total = rows * c;
+  const int dr = CS_ROWS / c, dc = CS_ROWS % c;
+  int r = threadIdx.x / c, k = threadIdx.x % c;
+  for (int q = threadIdx.x; q < total; q += CS_ROWS) {
+    p[q] = (T)lds[r * cs + k];
+    r += dr; k += dc;
+    if (k >= c) { k -= c; ++r; }
+  }
+}
+
+__device__ __forceinline__ int rows_of_block(int64_t n) {
+  const int64_t left = n - (int64_t)blockIdx.x * CS_ROWS;
+  return left < CS_ROWS ? (left > 0 ? (int)left : 0) : CS_ROWS;
+}
+
+// What both passes know of one row.  Logits: ps / pt the two softmaxes, ls / lt the log-softmaxes (kind 'kl').
+// Probabilities: ps / pt as given.  conf = the teacher's first maximum.
+struct RowPair {
+  float ps[kMaxClasses], pt[kMaxClasses], dl[kMaxClasses];      // dl = lt - ls ('kl' on logits)
+  float conf;
+};
+
+template <bool PROBS>
+__device__ __forceinline__ void row_pair(const float (&zs)[kMaxClasses], const float (&zt)[kMaxClasses], int c, int kind,
+                                         RowPair& R) {
+  if (PROBS) {
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < kMaxClasses; ++j)
+      if (j < c) { R.ps[j] = zs[j]; R.pt[j] = zt[j]; mx = fmaxf(mx, R.pt[j]); }
+    R.conf = mx;
+    return;
+  }
+  float mxs, ss, mxt, st;
+  row_softmax<float>(zs, c, R.ps, mxs, ss);
+  const int arg = row_softmax<float>(zt, c, R.pt, mxt, st);
+  R.conf = pick(R.pt, c, arg) / st;
+  const float lss = logf(ss), lst = logf(st);
+#pragma unroll
+  for (int j = 0; j < kMaxClasses; ++j)
+    if (j < c) {
+      R.ps[j] = R.ps[j] / ss;
+      R.pt[j] = R.pt[j] / st;
+      if (kind == KIND_KL) R.dl[j] = ((zt[j] - mxt) - lst) - ((zs[j] - mxs) - lss);
+    }
+}
+
+// the workgroup's rows of both operands, each thread's own pair into its registers, through ONE LDS image
+template <typename TS, typename TT>
+__device__ __forceinline__ void load_pair(const TS* __restrict__ zs_g, const TT* __restrict__ zt_g, int64_t row0, int nrows,
+                                          int c, int cs, float* __restrict__ rows, float (&zs)[kMaxClasses],
+                                          float (&zt)[kMaxClasses]) {
+  rows_in<TS>(zs_g, row0, nrows, c, cs, rows);
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < kMaxClasses; ++j) zs[j] = (j < c && (int)threadIdx.x < nrows) ? rows[threadIdx.x * cs + j] : 0.f;
+  __syncthreads();
+  rows_in<TT>(zt_g, row0, nrows, c, cs, rows);
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < kMaxClasses; ++j) zt[j] = (j < c && (int)threadIdx.x < nrows) ? rows[threadIdx.x * cs + j] : 0.f;
+}
+
+// r_i (masked) of every row, per_row (optional), and the workgroup's f64 partial in a fixed order
+template <typename TS, typename TT, bool PROBS>
+__global__ void __launch_bounds__(CS_ROWS) consistency_fwd_kernel(const TS* __restrict__ zs, const TT* __restrict__ zt,
+                                                                  int64_t n, int c, int kind, float min_conf,
+                                                                  float* __restrict__ per_row,
+                                                                  double* __restrict__ part) {
+  __shared__ float rows[CS_ROWS * (kMaxClasses + 1)];
+  __shared__ double red[CS_ROWS];
+  const int cs = c | 1;
+  const int64_t row0 = (int64_t)blockIdx.x * CS_ROWS;
+  const int nrows = rows_of_block(n);
+  float xs[kMaxClasses], xt[kMaxClasses];
+  load_pair<TS, TT>(zs, zt, row0, nrows, c, cs, rows, xs, xt);
+  float r = 0.f;
+  if ((int)threadIdx.x < nrows) {
+    float* mine = rows + threadIdx.x * cs;
+    RowPair R;
+    row_pair<PROBS>(xs, xt, c, kind, R);
+    if (R.conf >= min_conf) {                               // (a NaN confidence masks the row)
+#pragma unroll
+      for (int j = 0; j < kMaxClasses; ++j)
+        if (j < c) {
+          if (kind == KIND_MSE) {
+            const float d = R.ps[j] - R.pt[j];
+            mine[j] = d * d;
+          } else {
+            mine[j] = R.pt[j] == 0.f ? 0.f : R.pt[j] * R.dl[j];
+          }
+        }
+      r = np_sum_f32(mine, c);                              // (the thread's own LDS row: no one else reads it any more)
+    }
+    if (per_row != nullptr) per_row[row0 + threadIdx.x] = r;
+  }
+  red[threadIdx.x] = (double)r;
+  __syncthreads();
+  for (int w = CS_ROWS / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
+// out2 = {sum / denom, sum}: one workgroup, fixed order
+__global__ void __launch_bounds__(256) consistency_final_kernel(const double* __restrict__ part, int64_t nblocks,
+                                                                double denom, double* __restrict__ out2) {
+  __shared__ double red[256];
+  double a = 0.0;
+  for (int64_t i = threadIdx.x; i < nblocks; i += 256) a += part[i];
+  red[threadIdx.x] = a;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out2[0] = red[0] / denom;
+    out2[1] = red[0];
+  }
+}
+
+// dz of every row; k1 = the scale of the objective as f32: 1 / (n c) ('mse' on logits), 2 / (n c) ('mse' on
+// probabilities), 1 / n ('kl'); coef = g * k1 is ONE f32 product, and so is every product below.
+template <typename TS, typename TT, bool PROBS>
+__global__ void __launch_bounds__(CS_ROWS) consistency_bwd_kernel(const TS* __restrict__ zs, const TT* __restrict__ zt,
+                                                                  int64_t n, int c, int kind, float min_conf, float k1,
+                                                                  const float* __restrict__ grad_scale,
+                                                                  TS* __restrict__ dz) {
+  __shared__ float rows[CS_ROWS * (kMaxClasses + 1)];
+  const int cs = c | 1;
+  const int64_t row0 = (int64_t)blockIdx.x * CS_ROWS;
+  const int nrows = rows_of_block(n);
+  float xs[kMaxClasses], xt[kMaxClasses];
+  load_pair<TS, TT>(zs, zt, row0, nrows, c, cs, rows, xs, xt);
+  if ((int)threadIdx.x < nrows) {
+    float* mine = rows + threadIdx.x * cs;
+    const float coef = grad_scale[0] * k1;
+    RowPair R;
+    row_pair<PROBS>(xs, xt, c, kind, R);
+    const bool on = R.conf >= min_conf;
+    float dot = 0.f;
+    if (!PROBS && kind == KIND_MSE) {
+#pragma unroll
+      for (int j = 0; j < kMaxClasses; ++j)
+        if (j < c) dot = dot + R.ps[j] * (2.f * (R.ps[j] - R.pt[j]));
+    }
+#pragma unroll
+    for (int j = 0; j < kMaxClasses; ++j)
+      if (j < c) {
+        const float d = R.ps[j] - R.pt[j];
+        float g;
+        if (PROBS || kind == KIND_KL) g = coef * d;
+        else g = coef * (R.ps[j] * (2.f * d - dot));
+        mine[j] = on ? g : 0.f;
+      }
+  }
+  __syncthreads();
+  rows_out<TS>(dz, row0, nrows, c, cs, rows);
+}
+
+int consistency_check(const char* what, int64_t n, int c, int s_dtype, int t_dtype, int kind, int is_probs) {
+  LIDAL_REQUIRE(c >= 1 && c <= kMaxClasses, "%s: classes must be in 1..%d (got %d)", what, kMaxClasses, c);
+  LIDAL_REQUIRE(n >= 0 && n * (int64_t)c < (1ll << 30), "%s: %lld rows x %d classes reach 2^30 entries", what,
+                (long long)n, c);
+  LIDAL_REQUIRE(kind == KIND_MSE || kind == KIND_KL, "%s: kind must be 0 (mse) or 1 (kl), got %d", what, kind);
+  LIDAL_REQUIRE(s_dtype == LIDAL_F32 || s_dtype == LIDAL_BF16, "%s: bad student dtype %d", what, s_dtype);
+  LIDAL_REQUIRE(t_dtype == LIDAL_F32 || t_dtype == LIDAL_BF16, "%s: bad teacher dtype %d", what, t_dtype);
+  LIDAL_REQUIRE(!is_probs || (kind == KIND_MSE && s_dtype == LIDAL_F32 && t_dtype == LIDAL_F32),
+                "%s: probabilities are f32 and take 'mse' only", what);
+  return 0;
+}
+
+struct ConsistencyWs {
+  double* part;
+  int64_t nb, total;
+};
+
+ConsistencyWs consistency_layout(void* base, int64_t n) {
+  ConsistencyWs w;
+  w.nb = cdiv(n > 0 ? n : 1, CS_ROWS);
+  Carver cv(base);
+  w.part = cv.take<double>(w.nb);
+  w.total = cv.total();
+  return w;
+}
+
+}  // namespace
+}  // namespace lidal
+
+using namespace lidal;
+
+extern "C" int lidal_ema_chunk_elems(void) { return kEmaChunk; }
+
+extern "C" int lidal_ema_step(const void* table, int n_recs, int64_t v_end, double one_minus_alpha, int all_copy,
+                              void* stream) {
+  LIDAL_REQUIRE(n_recs >= 0 && v_end >= 0, "lidal_ema_step: %d records, virtual end %lld", n_recs, (long long)v_end);
+  LIDAL_REQUIRE(table != nullptr || n_recs == 0, "lidal_ema_step: null table");
+  LIDAL_REQUIRE(one_minus_alpha >= 0.0 && one_minus_alpha <= 1.0, "lidal_ema_step: 1 - alpha = %g is outside [0, 1]",
+                one_minus_alpha);
+  if (n_recs == 0 || v_end == 0) return 0;
+  const int64_t n_chunks = cdiv(v_end, kEmaChunk);
+  static int cus[MAX_DEVICES] = {0};
+  const int dev = current_device();
+  if (cus[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev] = n;
+  }
+  const int64_t cap = (int64_t)cus[dev] * kEmaBlocksPerCU;
+  const int grid = (int)(n_chunks < cap ? n_chunks : cap);
+  hipLaunchKernelGGL(ema_step_kernel, dim3(grid), dim3(kEmaThreads), 0, (hipStream_t)stream, (const EmaRec*)table, n_recs,
+                     n_chunks, (float)one_minus_alpha, all_copy);
+  LIDAL_CHECK_LAUNCH("lidal_ema_step");
+  return 0;
+}
+
+extern "C" int lidal_pseudo_labels(const void* logits, int dtype, int64_t nv, int c, const float* thresholds,
+                                   double threshold, const int64_t* inverse, const int64_t* labels, int64_t ignore_index,
+                                   int64_t p, int64_t* out, int64_t* stats, float* conf, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  LIDAL_REQUIRE(c >= 1 && c <= kMaxClasses, "pseudo_labels: classes must be in 1..%d (got %d)", kMaxClasses, c);
+  LIDAL_REQUIRE(nv >= 0 && p >= 0 && nv * (int64_t)c < (1ll << 40), "pseudo_labels: %lld rows, %lld points",
+                (long long)nv, (long long)p);
+  LIDAL_REQUIRE(inverse != nullptr || p == nv, "pseudo_labels: without an inverse map there is one point per row");
+  LIDAL_REQUIRE(dtype == LIDAL_F32 || dtype == LIDAL_BF16, "pseudo_labels: bad dtype %d", dtype);
+  LIDAL_REQUIRE(stats != nullptr && (out != nullptr || p == 0) && (logits != nullptr || nv == 0),
+                "pseudo_labels: null output or logits");
+  LIDAL_HIP(hipMemsetAsync(stats, 0, (size_t)(c + 2) * 8, s));
+  if (p == 0) return 0;
+  const unsigned nb = (unsigned)cdiv(p, PL_THREADS);
+  if (dtype == LIDAL_F32)
+    pseudo_labels_kernel<float><<<nb, PL_THREADS, 0, s>>>((const float*)logits, nv, c, thresholds, (float)threshold,
+                                                          inverse, labels, ignore_index, p, out,
+                                                          (unsigned long long*)stats, conf);
+  else
+    pseudo_labels_kernel<__bf16><<<nb, PL_THREADS, 0, s>>>((const __bf16*)logits, nv, c, thresholds, (float)threshold,
+                                                           inverse, labels, ignore_index, p, out,
+                                                           (unsigned long long*)stats, conf);
+  LIDAL_CHECK_LAUNCH("pseudo_labels");
+  return 0;
+}
+
+extern "C" int64_t lidal_consistency_workspace_bytes(int64_t n) {
+  if (n < 0) return 0;
+  return consistency_layout(nullptr, n).total;
+}
+
+extern "C" int lidal_consistency_fwd(const void* student, int s_dtype, const void* teacher, int t_dtype, int64_t n, int c,
+                                     int kind, int is_probs, double min_conf, double* out2, float* per_row, void* ws,
+                                     int64_t ws_bytes, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = consistency_check("consistency_fwd", n, c, s_dtype, t_dtype, kind, is_probs)) return rc;
+  LIDAL_REQUIRE(n > 0 && student != nullptr && teacher != nullptr && out2 != nullptr && ws != nullptr,
+                "consistency_fwd: no rows or a null operand");
+  const ConsistencyWs w = consistency_layout(ws, n);
+  LIDAL_REQUIRE(ws_bytes >= w.total, "consistency workspace too small: %lld < %lld", (long long)ws_bytes,
+                (long long)w.total);
+  const unsigned nb = (unsigned)w.nb;
+  const float mc = (float)min_conf;
+#define LIDAL_CS_FWD(TS, TT, P) \
+  consistency_fwd_kernel<TS, TT, P><<<nb, CS_ROWS, 0, s>>>((const TS*)student, (const TT*)teacher, n, c, kind, mc, per_row, w.part)
+  if (is_probs) LIDAL_CS_FWD(float, float, true);
+  else if (s_dtype == LIDAL_F32 && t_dtype == LIDAL_F32) LIDAL_CS_FWD(float, float, false);
+  else if (s_dtype == LIDAL_F32) LIDAL_CS_FWD(float, __bf16, false);
+  else if (t_dtype == LIDAL_F32) LIDAL_CS_FWD(__bf16, float, false);
+  else LIDAL_CS_FWD(__bf16, __bf16, false);
+#undef LIDAL_CS_FWD
+  LIDAL_CHECK_LAUNCH("consistency_fwd");
+  const double denom = kind == KIND_MSE ? (double)n * (double)c : (double)n;
+  consistency_final_kernel<<<1, 256, 0, s>>>(w.part, w.nb, denom, out2);
+  LIDAL_CHECK_LAUNCH("consistency_final");
+  return 0;
+}
+
+extern "C" int lidal_consistency_bwd(const void* student, int s_dtype, const void* teacher, int t_dtype, int64_t n, int c,
+                                     int kind, int is_probs, double min_conf, const float* grad_scale, void* dz,
+                                     void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = consistency_check("consistency_bwd", n, c, s_dtype, t_dtype, kind, is_probs)) return rc;
+  LIDAL_REQUIRE(n > 0 && student != nullptr && teacher != nullptr && grad_scale != nullptr && dz != nullptr,
+                "consistency_bwd: no rows or a null operand");
+  const unsigned nb = (unsigned)cdiv(n, CS_ROWS);
+  const float mc = (float)min_conf;
+  const double nd = (double)n;
+  const float k1 = kind == KIND_KL ? (float)(1.0 / nd) : (float)((is_probs ? 2.0 : 1.0) / (nd * (double)c));
+#define LIDAL_CS_BWD(TS, TT, P) \
+  consistency_bwd_kernel<TS, TT, P><<<nb, CS_ROWS, 0, s>>>((const TS*)student, (const TT*)teacher, n, c, kind, mc, k1, grad_scale, (TS*)dz)
+  if (is_probs) LIDAL_CS_BWD(float, float, true);
+  else if (s_dtype == LIDAL_F32 && t_dtype == LIDAL_F32) LIDAL_CS_BWD(float, float, false);
+  else if (s_dtype == LIDAL_F32) LIDAL_CS_BWD(float, __bf16, false);
+  else if (t_dtype == LIDAL_F32) LIDAL_CS_BWD(__bf16, float, false);
+  else LIDAL_CS_BWD(__bf16, __bf16, false);
+#undef LIDAL_CS_BWD
+  LIDAL_CHECK_LAUNCH("consistency_bwd");
+  return 0;
+}
