@@ -888,6 +888,39 @@ int lidal_adam_chunk_elems(void);
 int lidal_adam_step(const void* table, int rec_begin, int rec_end, int64_t v_begin, int64_t v_end, const void* grad_base,
                     float* m, float* v, int64_t state_numel, double one_minus_beta1, double beta2, double one_minus_beta2,
                     double bias_correction2_sqrt, double eps, double neg_step_size, double weight_decay, void* stream);
+/* The same launch (table, records, virtual axis, grad_base, state buffers: all as lidal_adam_step) for the two forms
+ * lidal_adam_step does not have:
+ *   decoupled != 0: AdamW, torch's decoupled_weight_decay=True -- p = p * (float)decay_factor first (the host passes
+ *     1 - lr * weight_decay), then the five lines with g = grad; `weight_decay` itself is not used;
+ *   clip_coef != NULL (device, one float): g = grad * *clip_coef, rounded, before anything else -- also when it is 1.
+ *     The gradient itself is not written.
+ * decoupled == 0 needs clip_coef (the coupled form without clipping IS lidal_adam_step). */
+int lidal_adam_step_ex(const void* table, int rec_begin, int rec_end, int64_t v_begin, int64_t v_end, const void* grad_base,
+                       float* m, float* v, int64_t state_numel, double one_minus_beta1, double beta2,
+                       double one_minus_beta2, double bias_correction2_sqrt, double eps, double neg_step_size,
+                       double weight_decay, int decoupled, double decay_factor, const float* clip_coef, void* stream);
+/* SGD over the same table in one launch -- torch's _single_tensor_sgd, every operation rounded separately in f32:
+ *     g = grad (* *clip_coef if clip_coef != NULL) (+ weight_decay * p if weight_decay != 0)
+ *     momentum != 0:  buf = g (first_step != 0: buf is written, not read)  or  buf = buf * momentum + one_minus_dampening * g;
+ *                     g = g + momentum * buf (nesterov != 0)  or  g = buf
+ *     p = p + neg_lr * g
+ * `momentum_buffer` [state_numel] is the ONE flat state buffer (the table's state word indexes it); with momentum == 0
+ * it may be NULL and nothing but p and the gradient is touched. */
+int lidal_sgd_step(const void* table, int rec_begin, int rec_end, int64_t v_begin, int64_t v_end, const void* grad_base,
+                   float* momentum_buffer, int64_t state_numel, double momentum, double one_minus_dampening, double neg_lr,
+                   double weight_decay, int nesterov, int first_step, const float* clip_coef, void* stream);
+/* The global gradient norm of torch's clip_grad_norm_ without a read-back.  lidal_grad_norm_partials writes, for records
+ * [rec_begin, rec_end) of the table, the f64 sum of g * g of every block of lidal_grad_norm_block_elems() elements of
+ * every tensor: block j of record r goes to partials[slot_start[r] + j], slot_start (device, int64 [records + 1]) being
+ * the running sum of ceil(n_r / block) and n_slots its last entry (the size of `partials`).  The order of the additions
+ * is a function of the record and the element's index inside its tensor only (csrc/optim.hip): not of the grid, the
+ * addresses or grad_base.  zero != 0 writes 0 to those slots instead (records that have no gradient this step).
+ * lidal_grad_norm_finish (one workgroup) adds the n_slots partials in ascending order and writes
+ *     out[0] = total = (float)sqrt(sum),   out[1] = min((float)max_norm / (total + 1e-6f), 1)   (a NaN stays a NaN). */
+int lidal_grad_norm_block_elems(void);
+int lidal_grad_norm_partials(const void* table, const int64_t* slot_start, int rec_begin, int rec_end,
+                             const void* grad_base, double* partials, int64_t n_slots, int zero, void* stream);
+int lidal_grad_norm_finish(const double* partials, int64_t n_slots, double max_norm, float* out, void* stream);
 
 /* ---- the mean-teacher step (csrc/semi.hip; not plan operations: all of it is the caller's loop) ------------ */
 /* The teacher as an exponential moving average of the student over any number of tensors in ONE launch, no

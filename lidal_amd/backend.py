@@ -188,6 +188,11 @@ SIGNATURES = {
     'lidal_cast_rows_bf16': (_i32, [_vp, _i32, _vp, _i32, _i64, _vp]),
     'lidal_adam_chunk_elems': (_i32, []),
     'lidal_adam_step': (_i32, [_vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _vp]),
+    'lidal_adam_step_ex': (_i32, [_vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _i32, _f64, _vp, _vp]),
+    'lidal_sgd_step': (_i32, [_vp, _i32, _i32, _i64, _i64, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i32, _i32, _vp, _vp]),
+    'lidal_grad_norm_block_elems': (_i32, []),
+    'lidal_grad_norm_partials': (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp]),
+    'lidal_grad_norm_finish': (_i32, [_vp, _i64, _f64, _vp, _vp]),
     'lidal_ema_chunk_elems': (_i32, []),
     'lidal_ema_step': (_i32, [_vp, _i32, _i64, _f64, _i32, _vp]),
     'lidal_pseudo_labels': (_i32, [_vp, _i32, _i64, _i32, _vp, _f64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
