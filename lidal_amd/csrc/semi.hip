@@ -9,7 +9,7 @@
 //
 // The row softmax everywhere is view_row_softmax of score.hip, restated for f32 and bf16 rows: first maximum,
 // expf(x - mx), running f32 sum in class order, f32 divide.
-#include "common.h"
+#include "multi_tensor.h"
 #include "npsum.h"
 
 #pragma clang fp contract(off)
@@ -21,17 +21,8 @@ using npsum::kMaxClasses;
 using npsum::np_sum_f32;
 
 // ---------------------------------------------------------------------------------------------------------- EMA
-// t = t + (s - t) * oma per f32 element (kind 0), or a copy of 32-bit words with no arithmetic on them (kind 1).  The
-// layout of the work is adam_step_kernel's (optim.hip): one record per tensor on a virtual axis of 32-bit words, cut into
-// chunks; a workgroup takes a run of chunks.  vstart = (teacher address / 4) mod 32 makes chunk boundaries 128-byte
-// boundaries of the large tensors; where teacher and student share a 16-byte phase a piece moves as 16-byte accesses
-// (a whole chunk: all loads before the first use), otherwise -- and for the up to three words before / after the whole
-// vectors -- as 4-byte accesses.
-constexpr int kEmaThreads = 256;
-constexpr int kEmaVecs = 4;
-constexpr int kEmaChunk = kEmaThreads * kEmaVecs * 4;       // 32-bit words
-constexpr int kEmaBlocksPerCU = 4;
-
+// t = t + (s - t) * oma per f32 element (kind 0), or a copy of 32-bit words with no arithmetic on them (kind 1), over the
+// record table, virtual axis (vstart from the teacher's address), chunk walk and piece mover of multi_tensor.h.
 struct EmaRec {             // five 64-bit words: the table's record
   uint64_t t;               // address of the teacher's tensor
   uint64_t s;               // address of the student's
@@ -40,94 +31,44 @@ struct EmaRec {             // five 64-bit words: the table's record
   int64_t kind;             // 0: lerp (f32), 1: copy
 };
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#if defined(__HIP_DEVICE_COMPILE__)
-#define LIDAL_GLOBAL __attribute__((address_space(1)))
-#else
-#define LIDAL_GLOBAL
-#endif
-typedef LIDAL_GLOBAL unsigned gword;
-typedef LIDAL_GLOBAL const unsigned cgword;
-typedef LIDAL_GLOBAL u32x4 gword4;
-typedef LIDAL_GLOBAL const u32x4 cgword4;
-
 __device__ __forceinline__ unsigned ema_word(unsigned t, unsigned s, float oma) {
   const float tf = __uint_as_float(t), sf = __uint_as_float(s);
   return __float_as_uint(tf + (sf - tf) * oma);
 }
 
-__device__ __forceinline__ u32x4 ema_vec(const u32x4& t, const u32x4& s, float oma) {
-  u32x4 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) r[e] = ema_word(t[e], s[e], oma);
-  return r;
+// The two rules for multi_tensor::move_piece, on words: array 0 the teacher, 1 the student (never written).
+struct EmaLerp {
+  typedef unsigned Elem;
+  static constexpr int kArrays = 2;
+  static constexpr unsigned kLoads = 3, kStores = 1;
+  float oma;
+  __device__ __forceinline__ void update(unsigned (&x)[2]) const { x[0] = ema_word(x[0], x[1], oma); }
+};
+
+struct EmaCopy {            // the teacher is written, never read
+  typedef unsigned Elem;
+  static constexpr int kArrays = 2;
+  static constexpr unsigned kLoads = 2, kStores = 1;
+  __device__ __forceinline__ void update(unsigned (&x)[2]) const { x[0] = x[1]; }
+};
+
+template <typename Rule>
+__device__ __forceinline__ void ema_piece(const Rule& rule, const EmaRec& R, int64_t a, int64_t e) {
+  multi_tensor::Arrays<Rule> A;
+  A.p[0] = (LIDAL_GLOBAL unsigned*)R.t;
+  A.p[1] = (LIDAL_GLOBAL unsigned*)R.s;
+  multi_tensor::move_piece(rule, A, a, e);
 }
 
-// words [a, b) of one tensor (b - a <= kEmaChunk), by the whole workgroup
-template <bool COPY>
-__device__ __forceinline__ void ema_piece(gword* t, cgword* s, int64_t a, int64_t b, float oma) {
-  const int tid = threadIdx.x;
-  const uintptr_t ta = (uintptr_t)(t + a);
-  if (((ta ^ (uintptr_t)(s + a)) & 15) != 0) {
-    for (int64_t i = a + tid; i < b; i += kEmaThreads) t[i] = COPY ? s[i] : ema_word(t[i], s[i], oma);
-    return;
-  }
-  int64_t head = (int64_t)(((16 - (ta & 15)) & 15) >> 2);         // words before the first 16-byte boundary
-  if (head > b - a) head = b - a;
-  const int64_t v0 = a + head;
-  const int64_t nvec = (b - v0) >> 2;
-  const int64_t tail = v0 + nvec * 4;
-  gword4* t4 = (gword4*)(t + v0);
-  cgword4* s4 = (cgword4*)(s + v0);
-  if (nvec == kEmaThreads * kEmaVecs) {                           // a whole chunk: every load before the first use
-    u32x4 tt[kEmaVecs], ss[kEmaVecs];
-#pragma unroll
-    for (int j = 0; j < kEmaVecs; ++j) {
-      const int i = tid + j * kEmaThreads;
-      ss[j] = s4[i];
-      if (!COPY) tt[j] = t4[i];
-    }
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < kEmaVecs; ++j) t4[tid + j * kEmaThreads] = COPY ? ss[j] : ema_vec(tt[j], ss[j], oma);
-  } else {
-    for (int64_t i = tid; i < nvec; i += kEmaThreads) {
-      const u32x4 ss = s4[i];
-      t4[i] = COPY ? ss : ema_vec(t4[i], ss, oma);
-    }
-  }
-  if (tid < head) t[a + tid] = COPY ? s[a + tid] : ema_word(t[a + tid], s[a + tid], oma);
-  if (tid < b - tail) t[tail + tid] = COPY ? s[tail + tid] : ema_word(t[tail + tid], s[tail + tid], oma);
-}
-
-__global__ __launch_bounds__(kEmaThreads) void ema_step_kernel(const EmaRec* __restrict__ recs, int n_recs,
-                                                               int64_t n_chunks, float oma, int all_copy) {
-  const int64_t c0 = n_chunks * (int64_t)blockIdx.x / gridDim.x, c1 = n_chunks * ((int64_t)blockIdx.x + 1) / gridDim.x;
-  if (c0 >= c1) return;
-  // first record that ends behind the start of chunk c0 (all of this is uniform over the workgroup)
-  const int64_t first = c0 * kEmaChunk;
-  int lo = 0, hi = n_recs;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (recs[mid].vstart + recs[mid].n <= first) lo = mid + 1; else hi = mid;
-  }
-  int r = lo;
-  for (int64_t c = c0; c < c1; ++c) {
-    const int64_t cs = c * kEmaChunk, ce = cs + kEmaChunk;
-    while (r < n_recs && recs[r].vstart + recs[r].n <= cs) ++r;
-    for (int q = r; q < n_recs; ++q) {
-      const EmaRec R = recs[q];
-      if (R.vstart >= ce) break;
-      if (R.n <= 0) continue;
-      const int64_t a = (cs > R.vstart ? cs : R.vstart) - R.vstart;
-      const int64_t e = (ce < R.vstart + R.n ? ce : R.vstart + R.n) - R.vstart;
-      if (all_copy || R.kind != 0)
-        ema_piece<true>((gword*)R.t, (cgword*)R.s, a, e, oma);
-      else
-        ema_piece<false>((gword*)R.t, (cgword*)R.s, a, e, oma);
-    }
-  }
+__global__ __launch_bounds__(multi_tensor::kThreads) void ema_step_kernel(const EmaRec* __restrict__ recs, int n_recs,
+                                                                          int64_t n_chunks, float oma, int all_copy) {
+  multi_tensor::walk_chunks(recs, 0, n_recs, 0, n_chunks, [&](const EmaRec R, int64_t a, int64_t e) {
+    if (R.n <= 0) return;
+    if (all_copy || R.kind != 0)
+      ema_piece(EmaCopy{}, R, a, e);
+    else
+      ema_piece(EmaLerp{oma}, R, a, e);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------- rows
@@ -421,7 +362,7 @@ ConsistencyWs consistency_layout(void* base, int64_t n) {
 
 using namespace lidal;
 
-extern "C" int lidal_ema_chunk_elems(void) { return kEmaChunk; }
+extern "C" int lidal_ema_chunk_elems(void) { return multi_tensor::kChunk; }
 
 extern "C" int lidal_ema_step(const void* table, int n_recs, int64_t v_end, double one_minus_alpha, int all_copy,
                               void* stream) {
@@ -430,18 +371,9 @@ extern "C" int lidal_ema_step(const void* table, int n_recs, int64_t v_end, doub
   LIDAL_REQUIRE(one_minus_alpha >= 0.0 && one_minus_alpha <= 1.0, "lidal_ema_step: 1 - alpha = %g is outside [0, 1]",
                 one_minus_alpha);
   if (n_recs == 0 || v_end == 0) return 0;
-  const int64_t n_chunks = cdiv(v_end, kEmaChunk);
-  static int cus[MAX_DEVICES] = {0};
-  const int dev = current_device();
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus[dev] = n;
-  }
-  const int64_t cap = (int64_t)cus[dev] * kEmaBlocksPerCU;
-  const int grid = (int)(n_chunks < cap ? n_chunks : cap);
-  hipLaunchKernelGGL(ema_step_kernel, dim3(grid), dim3(kEmaThreads), 0, (hipStream_t)stream, (const EmaRec*)table, n_recs,
-                     n_chunks, (float)one_minus_alpha, all_copy);
+  const int64_t n_chunks = cdiv(v_end, multi_tensor::kChunk);
+  hipLaunchKernelGGL(ema_step_kernel, dim3(multi_tensor::grid_for(n_chunks)), dim3(multi_tensor::kThreads), 0,
+                     (hipStream_t)stream, (const EmaRec*)table, n_recs, n_chunks, (float)one_minus_alpha, all_copy);
   LIDAL_CHECK_LAUNCH("lidal_ema_step");
   return 0;
 }

@@ -1,9 +1,25 @@
-"""Do these gradients lie back to back in one buffer?  The planned step (network/plan.py) leaves every parameter
+"""Many tensors as one: where the tensors of a model go on the virtual axis of a one-launch kernel (place_on_axis), and
+whether gradients lie back to back in one buffer (BackToBack).  The planned step (network/plan.py) leaves every parameter
 gradient as a view of ONE flat f32 buffer with a fixed slot layout; data_parallel.DataParallel reduces that buffer as one
 tensor and optim.Adam addresses the gradients relative to it."""
 import torch
 
-__all__ = ['BackToBack']
+__all__ = ['BackToBack', 'LINE', 'place_on_axis']
+
+LINE = 32               # 32-bit words of a 128-byte line
+
+
+def place_on_axis(addrs, counts):
+    """Where tensors at byte addresses `addrs` of `counts` 32-bit words go on a virtual word axis (csrc/multi_tensor.h),
+    in the order given: each at the first free word that has the tensor's own phase in a 128-byte line, so that a chunk
+    boundary of the axis is a line boundary of every large tensor.  Returns (first word of every tensor, end)."""
+    offs = []
+    v = 0
+    for addr, n in zip(addrs, counts):
+        v += (addr // 4 - v) % LINE
+        offs.append(v)
+        v += n
+    return offs, v
 
 
 class BackToBack:

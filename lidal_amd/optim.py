@@ -38,11 +38,9 @@ import numpy as np
 import torch
 
 from . import backend as B
-from .flat import BackToBack
+from .flat import LINE, BackToBack, place_on_axis
 
 __all__ = ['Adam', 'AdamW', 'SGD']
-
-_LINE = 32              # elements of a 128-byte line: the virtual axis keeps every tensor's phase in it
 
 
 class _Group:
@@ -130,13 +128,8 @@ class _OneLaunch(torch.optim.Optimizer):
             g = _Group()
             g.params = list(group['params'])
             g.numels = [p.numel() for p in g.params]
-            g.offs = []
-            off = 0
-            for p, n in zip(g.params, g.numels):        # the state offset takes the parameter's phase in a 128-byte line
-                off += (p.data_ptr() // 4 - off) % _LINE
-                g.offs.append(off)
-                off += n
-            g.size = off
+            # the state offset takes the parameter's phase in a 128-byte line
+            g.offs, g.size = place_on_axis([p.data_ptr() for p in g.params], g.numels)
             g.device = g.params[0].device if g.params else torch.device('cpu')
             g.bufs = None
             g.steps = [0] * len(g.params)
@@ -224,7 +217,7 @@ class _OneLaunch(torch.optim.Optimizer):
         v = 0
         for g in rt:
             g.rec0 = r
-            v += -v % _LINE
+            v += -v % LINE
             g.vbase = v                         # virtual index = vbase + state offset
             offs += g.offs
             vstart += [v + o for o in g.offs]
@@ -384,7 +377,7 @@ class _OneLaunch(torch.optim.Optimizer):
                     self._insert_state(g, idx)
                 g.uniform = g.steps[0] if len(set(g.steps)) == 1 else None
             for i0, i1, key in runs:
-                v0 = (g.vbase + g.offs[i0]) & -_LINE
+                v0 = (g.vbase + g.offs[i0]) & -LINE
                 v1 = g.vbase + g.offs[i1 - 1] + g.numels[i1 - 1]
                 if v1 <= v0:
                     continue

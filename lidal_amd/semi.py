@@ -21,12 +21,12 @@ import torch
 from torch.autograd import Function
 
 from . import backend as B
+from .flat import place_on_axis
 
 __all__ = ['EmaTeacher', 'pseudo_labels', 'consistency_loss', 'consistency_forward', 'semi_train_step', 'ema_alpha',
            'MAX_CLASSES']
 
 MAX_CLASSES = 32
-_LINE = 32              # 32-bit words of a 128-byte line: the virtual axis keeps every teacher tensor's phase in it
 _KINDS = {'mse': 0, 'kl': 1}
 
 
@@ -164,16 +164,11 @@ class EmaTeacher:
         return pairs
 
     def _build_table(self, pairs, addrs, device):
-        recs = []
-        v = 0
-        for (name, t, s, kind), (at, as_) in zip(pairs, addrs):
-            n = t.numel() * (t.element_size() // 4)
-            if n == 0:                              # zero-element tensors are skipped
-                continue
-            v += (at // 4 - v) % _LINE              # the teacher's phase in a 128-byte line fixes the axis
-            recs.append((at, as_, v, n, kind))
-            v += n
-        self._v_end = v
+        live = [(at, as_, t.numel() * (t.element_size() // 4), kind)
+                for (name, t, s, kind), (at, as_) in zip(pairs, addrs) if t.numel()]    # zero-element tensors are skipped
+        # the teacher's phase in a 128-byte line fixes the axis
+        starts, self._v_end = place_on_axis([r[0] for r in live], [r[2] for r in live])
+        recs = [(at, as_, v, n, kind) for (at, as_, n, kind), v in zip(live, starts)]
         self._n_recs = len(recs)
         self._table = torch.from_numpy(np.array(recs, dtype=np.int64).reshape(-1, 5)).to(device) if recs else None
         self.table_uploads += 1

@@ -227,6 +227,78 @@ def test_kernels_equal_the_restatement_bit_for_bit(rule, flat):
         assert opt.table_uploads >= 1
 
 
+_OFF_PHASE_RULES = {
+    'adamw': ('adamw', dict(lr=3e-3, weight_decay=0.01), None),
+    'adamw_clipped': ('adamw', dict(lr=3e-3, weight_decay=0.01), 10),
+    'sgd_momentum_0': ('sgd', dict(lr=3e-3, weight_decay=0.01), None),
+    'sgd_momentum': ('sgd', dict(lr=1e-3, momentum=0.9, nesterov=True, weight_decay=1e-4), None),
+}
+_PATTERN = 0xA5A5A5A5
+
+
+@pytest.mark.parametrize('rule', list(_OFF_PHASE_RULES))
+def test_every_rule_at_one_phase_off_the_16_byte_grid(rule):
+    """The 16-byte path of every rule with a head and a tail: parameters of 1, 2, 3, 4, 5, 7, chunk - 1, chunk, chunk + 1
+    and 2 chunk + 3 elements are views that start 1, 2 or 3 elements behind a 16-byte boundary of one arena, their
+    gradients views at the same offsets of a second one, and the optimizer places the state at the parameter's phase: all
+    arrays of a rule share a phase that is not 0 (asserted).  Two steps, so SGD with momentum writes buf = g and then
+    reads it: p and every state array equal the restatement bit for bit, and no word of the arenas or of the state
+    buffers outside the views changed."""
+    kind, hyper, clip = _OFF_PHASE_RULES[rule]
+    c, nb = _chunk(), _block()
+    sizes = [1, 2, 3, 4, 5, 7, c - 1, c, c + 1, 2 * c + 3]
+    rng = np.random.default_rng(41)
+    starts, end = [], 0
+    for i, n in enumerate(sizes):
+        starts.append(((end + 4) & -4) + 1 + i % 3)          # (at least one arena word between two views)
+        end = starts[-1] + n
+    total = (end + 8) & -4
+    inside = np.zeros(total, bool)
+    for s, n in zip(starts, sizes):
+        inside[s:s + n] = True
+    host_p = np.full(total, _PATTERN, np.uint32).view(np.float32)
+    for s, n in zip(starts, sizes):
+        host_p[s:s + n] = rng.standard_normal(n).astype(np.float32)
+    arena_p = torch.from_numpy(host_p).to(DEV)
+    arena_g = torch.from_numpy(np.full(total, _PATTERN, np.uint32).view(np.float32)).to(DEV)
+    assert arena_p.data_ptr() % 16 == 0 and arena_g.data_ptr() % 16 == 0
+    params = [torch.nn.Parameter(arena_p[s:s + n]) for s, n in zip(starts, sizes)]
+    opt = _make(kind, params, clip_grad_norm=clip, **hyper)
+    refs = [_Ref(kind, _np(p)) for p in params]
+    for step in (1, 2):
+        host_g = np.full(total, _PATTERN, np.uint32).view(np.float32)
+        for s, n in zip(starts, sizes):
+            host_g[s:s + n] = _edge_gradient(rng, n)
+        arena_g.copy_(torch.from_numpy(host_g))
+        grads = [host_g[s:s + n] for s, n in zip(starts, sizes)]
+        for p, s, n in zip(params, starts, sizes):
+            p.grad = arena_g[s:s + n]
+        coef = None
+        if clip is not None:
+            coef = optim_ref.clip_coef(optim_ref.grad_norm(grads, nb), clip)
+            assert coef < 1
+        opt.step()
+        for i, p in enumerate(params):
+            phase = p.data_ptr() % 16
+            assert phase == 4 * (1 + i % 3) and p.grad.data_ptr() % 16 == phase
+            for key, t in opt.state.get(p, {}).items():
+                if key != 'step':
+                    assert t.data_ptr() % 16 == phase, (key, i)
+            refs[i].step(grads[i], hyper, coef)
+            refs[i].check(opt, p, (step, i, sizes[i]))
+        assert _same_bits(_np(arena_g), host_g)
+        assert (adam_ref.bits(_np(arena_p))[~inside] == _PATTERN).all()
+        g = opt._rt[0]
+        used = np.zeros(max(g.size, 1), bool)
+        for o, n in zip(g.offs, g.numels):
+            used[o:o + n] = True
+        for buf in g.bufs or []:
+            assert not adam_ref.bits(_np(buf))[~used].any()
+    n_state = {'adamw': 2, 'sgd': 1 if hyper.get('momentum') else 0}[kind]
+    assert len(opt._rt[0].bufs or []) == n_state
+    assert opt.launches == 2 * (1 if clip is None else 3)
+
+
 # ---- edges of the norm ----------------------------------------------------------------------------------------------------
 def _one_clipped_step(kind, kw, sizes, grads, monkeypatch=None):
     """A single clipped step of `kind` over tensors of `sizes` (grads[i] None: no gradient) beside the restatement."""
