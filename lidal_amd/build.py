@@ -37,7 +37,7 @@ def _compile(src):
     obj = os.path.join(OBJ, src + '.o')
     deps = [os.path.join(CSRC, src), os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'grid.h'),
             os.path.join(CSRC, 'npsum.h'), os.path.join(CSRC, 'kmeans.h'), os.path.join(CSRC, 'sym3.h'), os.path.join(CSRC, 'scan.h'),
-            os.path.join(CSRC, 'multi_tensor.h'),
+            os.path.join(CSRC, 'multi_tensor.h'), os.path.join(CSRC, 'rows.h'),
             os.path.join(HERE, '..', 'include', 'lidal_amd.h'), os.path.abspath(__file__)]
     if _stale(obj, deps):
         cmd = ['hipcc'] + FLAGS + NO_PACKED_F32 + (['-ffp-contract=off'] if src in NO_CONTRACT else []) + \

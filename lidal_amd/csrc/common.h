@@ -62,6 +62,15 @@ __host__ __device__ static inline int64_t align_up(int64_t a, int64_t b) { retur
 
 constexpr int kWave = 64;
 
+// f(T{}) with T = float or __bf16 for the dtype code of the C ABI, and its int result; "name: bad dtype" for any other
+template <typename F>
+inline int with_dtype(int dtype, const char* name, F f) {
+  if (dtype == LIDAL_F32) return f(float{});
+  if (dtype == LIDAL_BF16) return f(__bf16{});
+  set_error("%s: bad dtype %d", name, dtype);
+  return 2;
+}
+
 // ---- workspace layout: regions of 256-byte granularity taken one after the other from `base` ----
 // A null base makes it a pure size computation, so ONE layout function per builder serves both its
 // lidal_X_workspace_bytes (the total) and its entry point (the pointers): the two cannot drift apart.

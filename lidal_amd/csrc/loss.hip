@@ -24,95 +24,16 @@
 // atomics anywhere: every sum has one fixed order, so two runs give the same bits.  A class's entries are the ranks
 // [k * n_valid, (k + 1) * n_valid) of the sorted list, so class and rank of an entry follow from its position.
 // Built without fma contraction (lidal_amd/build.py): jac and g are restated in numpy bit for bit (tests/loss_ref.py).
-#include "common.h"
+#include "rows.h"
 
 using namespace lidal;
+using namespace lidal::rows;
 
 namespace {
 
-constexpr int kMaxClasses = 32;
-constexpr int LV_ROWS = 256;                  // rows per workgroup of the row-wise passes
 constexpr int LV_ITEMS = 8;
 constexpr int LV_TILE = 256 * LV_ITEMS;       // ranks per workgroup of the rank passes
 constexpr int kFgBit = 30;                    // payload = row | fg << 30 (n * c < 2^30)
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-
-template <typename T> struct Vec16;
-template <> struct Vec16<float> {
-  static constexpr int N = 4;
-  typedef float4 vec;
-  __device__ static void unpack(const vec& v, float (&f)[4]) { f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w; }
-  __device__ static vec pack(const float (&f)[4]) { return make_float4(f[0], f[1], f[2], f[3]); }
-};
-template <> struct Vec16<__bf16> {
-  static constexpr int N = 8;
-  typedef bf16x8_t vec;
-  __device__ static void unpack(const vec& v, float (&f)[8]) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] = (float)v[i];
-  }
-  __device__ static vec pack(const float (&f)[8]) {
-    vec v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (__bf16)f[i];
-    return v;
-  }
-};
-
-// ---- rows through LDS: a workgroup's 256 rows are ONE contiguous piece of a [n, c] matrix, moved as 16-byte vectors
-// per lane whatever c is (the piece starts at a multiple of 256 * c elements: 16-byte aligned when the matrix is, which
-// `vec` says); in LDS the rows are c | 1 words apart, so that lanes reading their own row do not meet in one bank.
-__device__ __forceinline__ int lds_at(int e, int c, int cs) { return (e / c) * cs + (e % c); }
-
-template <typename T>
-__device__ __forceinline__ void rows_in(const T* __restrict__ src, int64_t row0, int rows, int c, int cs, bool vec,
-                                        float* __restrict__ lds) {
-  constexpr int V = Vec16<T>::N;
-  const T* p = src + row0 * c;
-  const int total = rows * c;
-  if (vec) {
-    for (int q = threadIdx.x * V; q < total; q += LV_ROWS * V) {
-      if (q + V <= total) {
-        float f[V];
-        Vec16<T>::unpack(*reinterpret_cast<const typename Vec16<T>::vec*>(p + q), f);
-#pragma unroll
-        for (int u = 0; u < V; ++u) lds[lds_at(q + u, c, cs)] = f[u];
-      } else {
-        for (int u = 0; q + u < total; ++u) lds[lds_at(q + u, c, cs)] = (float)p[q + u];
-      }
-    }
-  } else {
-    for (int q = threadIdx.x; q < total; q += LV_ROWS) lds[lds_at(q, c, cs)] = (float)p[q];
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ void rows_out(T* __restrict__ dst, int64_t row0, int rows, int c, int cs, bool vec,
-                                         const float* __restrict__ lds) {
-  constexpr int V = Vec16<T>::N;
-  T* p = dst + row0 * c;
-  const int total = rows * c;
-  if (vec) {
-    for (int q = threadIdx.x * V; q < total; q += LV_ROWS * V) {
-      if (q + V <= total) {
-        float f[V];
-#pragma unroll
-        for (int u = 0; u < V; ++u) f[u] = lds[lds_at(q + u, c, cs)];
-        *reinterpret_cast<typename Vec16<T>::vec*>(p + q) = Vec16<T>::pack(f);
-      } else {
-        for (int u = 0; q + u < total; ++u) p[q + u] = (T)lds[lds_at(q + u, c, cs)];
-      }
-    }
-  } else {
-    for (int q = threadIdx.x; q < total; q += LV_ROWS) p[q] = (T)lds[lds_at(q, c, cs)];
-  }
-}
-
-__device__ __forceinline__ int rows_of_block(int64_t n) {
-  const int64_t left = n - (int64_t)blockIdx.x * LV_ROWS;
-  return left < LV_ROWS ? (left > 0 ? (int)left : 0) : LV_ROWS;
-}
 
 // exclusive scan of one int per thread over a workgroup of NW waves; *total = the sum.  All threads call it.
 template <int NW>
@@ -138,33 +59,11 @@ __device__ __forceinline__ int block_scan_excl(int v, int* wsum /*[NW] LDS*/, in
   return base + incl - v;
 }
 
-__device__ __forceinline__ bool label_ok(int64_t y, int c, int64_t ignore_index) {
-  return y != ignore_index && y >= 0 && y < c;
-}
-
-// softmax of x[0 .. c) in place, f32.  The denominator is summed in f64 and rounded once: a sequential f32 sum of 32
-// terms is off by a few ulp, which every probability of the row (and twice the gradient) would inherit -- measured on
-// the separated inputs of tests/test_loss_gpu.py: 2.7e-7 relative l2 in dz at c = 32 against 4e-8 of torch on the CPU.
-__device__ __forceinline__ void softmax_row(float (&x)[kMaxClasses], int c) {
-  float mx = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < kMaxClasses; ++j)
-    if (j < c) mx = fmaxf(mx, x[j]);
-  double sd = 0.0;
-#pragma unroll
-  for (int j = 0; j < kMaxClasses; ++j)
-    if (j < c) { x[j] = expf(x[j] - mx); sd += (double)x[j]; }
-  const float s = (float)sd;
-#pragma unroll
-  for (int j = 0; j < kMaxClasses; ++j)
-    if (j < c) x[j] = x[j] / s;
-}
-
 // ---------------------------------------------------------------------------------------------- Lovasz-softmax
 // bcnt[b] = valid rows of block b | (a label outside [0, c) other than ignore_index) << 16
-__global__ void __launch_bounds__(LV_ROWS) lv_count_kernel(const int64_t* __restrict__ labels, int64_t n, int c,
-                                                           int64_t ignore_index, int* __restrict__ bcnt) {
-  const int64_t i = (int64_t)blockIdx.x * LV_ROWS + threadIdx.x;
+__global__ void __launch_bounds__(kRows) lv_count_kernel(const int64_t* __restrict__ labels, int64_t n, int c,
+                                                         int64_t ignore_index, int* __restrict__ bcnt) {
+  const int64_t i = (int64_t)blockIdx.x * kRows + threadIdx.x;
   bool ok = false, bad = false;
   if (i < n) {
     const int64_t y = labels[i];
@@ -199,18 +98,17 @@ __global__ void __launch_bounds__(1024) lv_offsets_kernel(int* __restrict__ bcnt
 }
 
 template <typename T, bool PROBS>
-__global__ void __launch_bounds__(LV_ROWS) lv_keys_kernel(const T* __restrict__ x, const int64_t* __restrict__ labels,
-                                                          int64_t n, int c, int64_t ignore_index, bool vec,
-                                                          const int* __restrict__ boff,
-                                                          const int64_t* __restrict__ counts,
-                                                          unsigned long long* __restrict__ keys,
-                                                          int* __restrict__ vals) {
-  __shared__ float rows[LV_ROWS * (kMaxClasses + 1)];
-  __shared__ int wcnt[LV_ROWS / 64];
-  const int cs = c | 1;
-  const int64_t row0 = (int64_t)blockIdx.x * LV_ROWS;
-  rows_in<T>(x, row0, rows_of_block(n), c, cs, vec, rows);
-  const int64_t i = row0 + threadIdx.x;
+__global__ void __launch_bounds__(kRows) lv_keys_kernel(const T* __restrict__ x, const int64_t* __restrict__ labels,
+                                                        int64_t n, int c, int64_t ignore_index, bool vec,
+                                                        const int* __restrict__ boff,
+                                                        const int64_t* __restrict__ counts,
+                                                        unsigned long long* __restrict__ keys,
+                                                        int* __restrict__ vals) {
+  __shared__ float lds[kTileFloats];
+  __shared__ int wcnt[kRows / 64];
+  const Tile tile(lds, n, c);
+  tile.load<T>(x, vec);
+  const int64_t i = tile.row0 + threadIdx.x;
   int64_t y = -1;
   bool ok = false;
   if (i < n) {
@@ -226,9 +124,7 @@ __global__ void __launch_bounds__(LV_ROWS) lv_keys_kernel(const T* __restrict__ 
   const int64_t nv = counts[1];
   const int64_t v = (int64_t)boff[blockIdx.x] + before;
   float p[kMaxClasses];
-#pragma unroll
-  for (int j = 0; j < kMaxClasses; ++j)
-    if (j < c) p[j] = rows[threadIdx.x * cs + j];
+  tile.own(p);
   // On logits the errors are rounded ONCE: the softmax runs in f64 on the f32 / bf16 logits and e = |fg - p| is taken
   // there, so the key's e is the f32 nearest to the exact error -- not 1 - (a p already off by an ulp or two of expf
   // and the division), which for p near 1 leaves e only a few significant bits.  With the f32 softmax the loss of one
@@ -397,32 +293,32 @@ __global__ void __launch_bounds__(64) lv_final_kernel(const double* __restrict__
 // (the first term: the gradient of the mean loss, the second: of the per-class losses L_k).
 //   PROBS: dx_k = G_k s_k;     logits: a_k = G_k s_k, dx_k = p_k (a_k - sum_j a_j p_j), j ascending
 template <typename T, bool PROBS>
-__global__ void __launch_bounds__(LV_ROWS) lv_bwd_kernel(const T* __restrict__ x, const int64_t* __restrict__ labels,
-                                                         int64_t n, int c, int64_t ignore_index, bool vec, bool gvec,
-                                                         int mode_all, const double* __restrict__ out,
-                                                         const float* __restrict__ grad,
-                                                         const float* __restrict__ gscale,
-                                                         const float* __restrict__ gclass, T* __restrict__ dx) {
-  __shared__ float rows[LV_ROWS * (kMaxClasses + 1)];
-  const int cs = c | 1;
-  const int64_t row0 = (int64_t)blockIdx.x * LV_ROWS;
-  const int nrows = rows_of_block(n);
-  const int64_t i = row0 + threadIdx.x;
+__global__ void __launch_bounds__(kRows) lv_bwd_kernel(const T* __restrict__ x, const int64_t* __restrict__ labels,
+                                                       int64_t n, int c, int64_t ignore_index, bool vec, bool gvec,
+                                                       int mode_all, const double* __restrict__ out,
+                                                       const float* __restrict__ grad,
+                                                       const float* __restrict__ gscale,
+                                                       const float* __restrict__ gclass, T* __restrict__ dx) {
+  __shared__ float lds[kTileFloats];
+  const Tile tile(lds, n, c);
+  const int64_t i = tile.row0 + threadIdx.x;
   const bool ok = i < n && label_ok(labels[i], c, ignore_index);
   float p[kMaxClasses], a[kMaxClasses];
   if (!PROBS) {
-    rows_in<T>(x, row0, nrows, c, cs, vec, rows);
+    tile.load<T>(x, vec);
     __syncthreads();
+    // The denominator is summed in f64 and rounded once: a sequential f32 sum of 32 terms is off by a few ulp, which
+    // every probability of the row (and twice the gradient) would inherit -- measured on the separated inputs of
+    // tests/test_loss_gpu.py: 2.7e-7 relative l2 in dz at c = 32 against 4e-8 of torch on the CPU.
     if (ok) {
-#pragma unroll
-      for (int j = 0; j < kMaxClasses; ++j)
-        if (j < c) p[j] = rows[threadIdx.x * cs + j];
-      softmax_row(p, c);
+      tile.own(p);
+      row_softmax<double>(p, c, p);
     }
     __syncthreads();
   }
-  rows_in<float>(grad, row0, nrows, c, cs, gvec, rows);
+  tile.load<float>(grad, gvec);
   __syncthreads();
+  tile.own(a);                        // G of the row
   const bool any = out[3] > 0.0;
   const float denom = mode_all ? (float)c : (float)out[1];
   const float gs = gscale != nullptr ? gscale[0] : 0.f;
@@ -435,16 +331,17 @@ __global__ void __launch_bounds__(LV_ROWS) lv_bwd_kernel(const T* __restrict__ x
         const bool counts_in = mode_all || out[4 + c + j] > 0.0;
         sk = (counts_in && denom > 0.f ? gs / denom : 0.f) + (gclass != nullptr ? gclass[j] : 0.f);
       }
-      a[j] = ok ? rows[threadIdx.x * cs + j] * sk : 0.f;
+      a[j] = ok ? a[j] * sk : 0.f;
       if (!PROBS && ok) dotd += (double)a[j] * (double)p[j];
     }
   const float dot = (float)dotd;
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < kMaxClasses; ++j)
-    if (j < c) rows[threadIdx.x * cs + j] = !ok ? 0.f : (PROBS ? a[j] : p[j] * (a[j] - dot));
+    if (j < c) a[j] = !ok ? 0.f : (PROBS ? a[j] : p[j] * (a[j] - dot));
+  tile.put(a);
   __syncthreads();
-  rows_out<T>(dx, row0, nrows, c, cs, vec, rows);
+  tile.store<T>(dx, vec);
 }
 
 struct LovaszWs {
@@ -461,7 +358,7 @@ struct LovaszWs {
 LovaszWs lovasz_layout(void* base, int64_t n, int c) {
   LovaszWs w;
   const int64_t q = n > 0 ? n : 1, m = q * c;
-  w.nb = cdiv(q, LV_ROWS);
+  w.nb = cdiv(q, kRows);
   w.nt = cdiv(q, LV_TILE);
   w.sort_bytes = radix_sort_ws_bytes(m, 8, true);
   Carver cv(base);
@@ -493,61 +390,38 @@ int lovasz_check(int64_t n, int c, int dtype, int is_probs) {
 // ---------------------------------------------------------------------------------------------- weighted cross-entropy
 // block partials {sum w[y] * -log softmax(x)[y], sum w[y]} in f64
 template <typename T>
-__global__ void __launch_bounds__(LV_ROWS) cew_fwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
-                                                          int64_t n, int c, int64_t ignore_index, bool vec,
-                                                          const float* __restrict__ weight, double* __restrict__ part) {
-  __shared__ float rows[LV_ROWS * (kMaxClasses + 1)];
-  __shared__ double red[2][LV_ROWS];
-  const int cs = c | 1;
-  const int64_t row0 = (int64_t)blockIdx.x * LV_ROWS;
-  rows_in<T>(logits, row0, rows_of_block(n), c, cs, vec, rows);
+__global__ void __launch_bounds__(kRows) cew_fwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                        int64_t n, int c, int64_t ignore_index, bool vec,
+                                                        const float* __restrict__ weight, double* __restrict__ part) {
+  __shared__ float lds[kTileFloats];
+  __shared__ double red[2][kRows];
+  const Tile tile(lds, n, c);
+  tile.load<T>(logits, vec);
   __syncthreads();
-  const int64_t i = row0 + threadIdx.x;
-  double loss = 0.0, wsum = 0.0;
+  const int64_t i = tile.row0 + threadIdx.x;
+  double v[2] = {0.0, 0.0};             // {w * nll, w} of the row
   if (i < n) {
     const int64_t y = labels[i];
     if (label_ok(y, c, ignore_index)) {
-      float x[kMaxClasses], mx = -INFINITY;
-#pragma unroll
-      for (int j = 0; j < kMaxClasses; ++j)
-        if (j < c) { x[j] = rows[threadIdx.x * cs + j]; mx = fmaxf(mx, x[j]); }
-      double sd = 0.0;
-      float xy = 0.f;
-#pragma unroll
-      for (int j = 0; j < kMaxClasses; ++j)
-        if (j < c) { sd += (double)expf(x[j] - mx); if (j == (int)y) xy = x[j]; }
+      float x[kMaxClasses], mx;
+      tile.own(x);
+      const float xy = pick(x, c, (int)y);
+      double sd;
+      row_exp<double>(x, c, x, mx, sd);
       const float w = weight[y];
-      loss = (double)(w * (logf((float)sd) + mx - xy));
-      wsum = (double)w;
+      v[0] = (double)(w * (logf((float)sd) + mx - xy));
+      v[1] = (double)w;
     }
   }
-  red[0][threadIdx.x] = loss; red[1][threadIdx.x] = wsum;
-  __syncthreads();
-  for (int w = LV_ROWS / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + w];
-      red[1][threadIdx.x] += red[1][threadIdx.x + w];
-    }
-    __syncthreads();
-  }
+  block_sum<2>(v, red);
   if (threadIdx.x == 0) { part[blockIdx.x * 2] = red[0][0]; part[blockIdx.x * 2 + 1] = red[1][0]; }
 }
 
 // out[0] = sum(w * nll) / sum(w) (0 / 0 = nan, as torch), out[1] = sum(w)          (single block, fixed order)
-__global__ void __launch_bounds__(256) cew_final_kernel(const double* __restrict__ part, int64_t nblocks,
-                                                        float* __restrict__ out) {
-  __shared__ double red[2][256];
-  double a = 0.0, b = 0.0;
-  for (int64_t i = threadIdx.x; i < nblocks; i += 256) { a += part[i * 2]; b += part[i * 2 + 1]; }
-  red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + w];
-      red[1][threadIdx.x] += red[1][threadIdx.x + w];
-    }
-    __syncthreads();
-  }
+__global__ void __launch_bounds__(kRows) cew_final_kernel(const double* __restrict__ part, int64_t nblocks,
+                                                          float* __restrict__ out) {
+  __shared__ double red[2][kRows];
+  sum_partials<2>(part, nblocks, red);
   if (threadIdx.x == 0) {
     out[0] = (float)(red[0][0] / red[1][0]);
     out[1] = (float)red[1][0];
@@ -556,33 +430,30 @@ __global__ void __launch_bounds__(256) cew_final_kernel(const double* __restrict
 
 // dlogits = w[y] (softmax - onehot) gscale / sum(w)   (0 for ignored rows)
 template <typename T>
-__global__ void __launch_bounds__(LV_ROWS) cew_bwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
-                                                          int64_t n, int c, int64_t ignore_index, bool vec,
-                                                          const float* __restrict__ weight,
-                                                          const float* __restrict__ fwd_out,
-                                                          const float* __restrict__ gscale, T* __restrict__ dlogits) {
-  __shared__ float rows[LV_ROWS * (kMaxClasses + 1)];
-  const int cs = c | 1;
-  const int64_t row0 = (int64_t)blockIdx.x * LV_ROWS;
-  const int nrows = rows_of_block(n);
-  rows_in<T>(logits, row0, nrows, c, cs, vec, rows);
+__global__ void __launch_bounds__(kRows) cew_bwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                        int64_t n, int c, int64_t ignore_index, bool vec,
+                                                        const float* __restrict__ weight,
+                                                        const float* __restrict__ fwd_out,
+                                                        const float* __restrict__ gscale, T* __restrict__ dlogits) {
+  __shared__ float lds[kTileFloats];
+  const Tile tile(lds, n, c);
+  tile.load<T>(logits, vec);
   __syncthreads();
-  const int64_t i = row0 + threadIdx.x;
+  const int64_t i = tile.row0 + threadIdx.x;
   const int64_t y = i < n ? labels[i] : ignore_index;
   const bool ok = i < n && label_ok(y, c, ignore_index);
   float x[kMaxClasses];
   if (ok) {
-#pragma unroll
-    for (int j = 0; j < kMaxClasses; ++j)
-      if (j < c) x[j] = rows[threadIdx.x * cs + j];
-    softmax_row(x, c);
+    tile.own(x);
+    row_softmax<double>(x, c, x);         // (f64 denominator: see lv_bwd_kernel)
   }
   const float k = ok ? weight[y] * (gscale[0] / fwd_out[1]) : 0.f;
 #pragma unroll
   for (int j = 0; j < kMaxClasses; ++j)
-    if (j < c) rows[threadIdx.x * cs + j] = ok ? (x[j] - (j == (int)y ? 1.f : 0.f)) * k : 0.f;
+    if (j < c) x[j] = ok ? (x[j] - (j == (int)y ? 1.f : 0.f)) * k : 0.f;
+  tile.put(x);
   __syncthreads();
-  rows_out<T>(dlogits, row0, nrows, c, cs, vec, rows);
+  tile.store<T>(dlogits, vec);
 }
 
 }  // namespace
@@ -604,20 +475,20 @@ extern "C" int lidal_lovasz_fwd(const void* x, int dtype, int is_probs, const in
     if (ranks != nullptr) LIDAL_HIP(hipMemsetAsync(ranks, 0xFF, (size_t)n * c * 4, s));      // ... have rank -1
   }
   const bool vec = aligned16(x);
-  lv_count_kernel<<<(unsigned)w.nb, LV_ROWS, 0, s>>>(labels, n, c, ignore_index, w.bcnt);
+  lv_count_kernel<<<(unsigned)w.nb, kRows, 0, s>>>(labels, n, c, ignore_index, w.bcnt);
   LIDAL_CHECK_LAUNCH("lovasz_count");
   lv_offsets_kernel<<<1, 1024, 0, s>>>(w.bcnt, w.nb, c, w.counts);
   LIDAL_CHECK_LAUNCH("lovasz_offsets");
   if (n > 0) {
     if (is_probs)
-      lv_keys_kernel<float, true><<<(unsigned)w.nb, LV_ROWS, 0, s>>>((const float*)x, labels, n, c, ignore_index, vec,
-                                                                     w.bcnt, w.counts, w.keys, w.vals);
+      lv_keys_kernel<float, true><<<(unsigned)w.nb, kRows, 0, s>>>((const float*)x, labels, n, c, ignore_index, vec,
+                                                                   w.bcnt, w.counts, w.keys, w.vals);
     else if (dtype == LIDAL_F32)
-      lv_keys_kernel<float, false><<<(unsigned)w.nb, LV_ROWS, 0, s>>>((const float*)x, labels, n, c, ignore_index, vec,
-                                                                      w.bcnt, w.counts, w.keys, w.vals);
+      lv_keys_kernel<float, false><<<(unsigned)w.nb, kRows, 0, s>>>((const float*)x, labels, n, c, ignore_index, vec,
+                                                                    w.bcnt, w.counts, w.keys, w.vals);
     else
-      lv_keys_kernel<__bf16, false><<<(unsigned)w.nb, LV_ROWS, 0, s>>>((const __bf16*)x, labels, n, c, ignore_index, vec,
-                                                                       w.bcnt, w.counts, w.keys, w.vals);
+      lv_keys_kernel<__bf16, false><<<(unsigned)w.nb, kRows, 0, s>>>((const __bf16*)x, labels, n, c, ignore_index, vec,
+                                                                     w.bcnt, w.counts, w.keys, w.vals);
     LIDAL_CHECK_LAUNCH("lovasz_keys");
     int class_bits = 0;
     while ((1 << class_bits) < c) ++class_bits;
@@ -644,22 +515,22 @@ extern "C" int lidal_lovasz_bwd(const void* x, int dtype, int is_probs, const in
   hipStream_t s = (hipStream_t)stream;
   if (int rc = lovasz_check(n, c, dtype, is_probs)) return rc;
   if (n == 0) return 0;
-  const unsigned nb = (unsigned)cdiv(n, LV_ROWS);
+  const unsigned nb = (unsigned)cdiv(n, kRows);
   const bool vec = aligned16(x) && aligned16(dx), gvec = aligned16(grad);
   if (is_probs)
-    lv_bwd_kernel<float, true><<<nb, LV_ROWS, 0, s>>>((const float*)x, labels, n, c, ignore_index, vec, gvec, mode_all, out,
-                                                      grad, grad_scale, grad_class, (float*)dx);
+    lv_bwd_kernel<float, true><<<nb, kRows, 0, s>>>((const float*)x, labels, n, c, ignore_index, vec, gvec, mode_all, out,
+                                                    grad, grad_scale, grad_class, (float*)dx);
   else if (dtype == LIDAL_F32)
-    lv_bwd_kernel<float, false><<<nb, LV_ROWS, 0, s>>>((const float*)x, labels, n, c, ignore_index, vec, gvec, mode_all,
-                                                       out, grad, grad_scale, grad_class, (float*)dx);
+    lv_bwd_kernel<float, false><<<nb, kRows, 0, s>>>((const float*)x, labels, n, c, ignore_index, vec, gvec, mode_all,
+                                                     out, grad, grad_scale, grad_class, (float*)dx);
   else
-    lv_bwd_kernel<__bf16, false><<<nb, LV_ROWS, 0, s>>>((const __bf16*)x, labels, n, c, ignore_index, vec, gvec, mode_all,
-                                                        out, grad, grad_scale, grad_class, (__bf16*)dx);
+    lv_bwd_kernel<__bf16, false><<<nb, kRows, 0, s>>>((const __bf16*)x, labels, n, c, ignore_index, vec, gvec, mode_all,
+                                                      out, grad, grad_scale, grad_class, (__bf16*)dx);
   LIDAL_CHECK_LAUNCH("lovasz_bwd");
   return 0;
 }
 
-extern "C" int64_t lidal_ce_weighted_workspace_bytes(int64_t n) { return cdiv(n > 0 ? n : 1, LV_ROWS) * 16 + 256; }
+extern "C" int64_t lidal_ce_weighted_workspace_bytes(int64_t n) { return cdiv(n > 0 ? n : 1, kRows) * 16 + 256; }
 
 extern "C" int lidal_ce_weighted_fwd(const void* logits, int dtype, const int64_t* labels, int64_t n, int c,
                                      int64_t ignore_index, const float* weight, float* out2, void* ws, int64_t ws_bytes,
@@ -668,20 +539,17 @@ extern "C" int lidal_ce_weighted_fwd(const void* logits, int dtype, const int64_
   LIDAL_REQUIRE(c >= 1 && c <= kMaxClasses, "weighted cross_entropy: classes must be in 1..%d", kMaxClasses);
   LIDAL_REQUIRE(n >= 0 && n * (int64_t)c < (1ll << 40), "weighted cross_entropy: %lld rows", (long long)n);
   LIDAL_REQUIRE(ws_bytes >= lidal_ce_weighted_workspace_bytes(n), "weighted cross_entropy workspace too small");
-  const int64_t blocks = cdiv(n > 0 ? n : 1, LV_ROWS);
+  const int64_t blocks = cdiv(n > 0 ? n : 1, kRows);
   const bool vec = aligned16(logits);
-  if (dtype == LIDAL_F32)
-    cew_fwd_kernel<float><<<(unsigned)blocks, LV_ROWS, 0, s>>>((const float*)logits, labels, n, c, ignore_index, vec,
-                                                               weight, (double*)ws);
-  else if (dtype == LIDAL_BF16)
-    cew_fwd_kernel<__bf16><<<(unsigned)blocks, LV_ROWS, 0, s>>>((const __bf16*)logits, labels, n, c, ignore_index, vec,
-                                                                weight, (double*)ws);
-  else {
-    set_error("weighted cross_entropy: bad dtype %d", dtype);
-    return 2;
-  }
-  LIDAL_CHECK_LAUNCH("ce_weighted_fwd");
-  cew_final_kernel<<<1, 256, 0, s>>>((const double*)ws, blocks, out2);
+  if (int rc = with_dtype(dtype, "weighted cross_entropy", [&](auto t) {
+        using T = decltype(t);
+        cew_fwd_kernel<T><<<(unsigned)blocks, kRows, 0, s>>>((const T*)logits, labels, n, c, ignore_index, vec, weight,
+                                                             (double*)ws);
+        LIDAL_CHECK_LAUNCH("ce_weighted_fwd");
+        return 0;
+      }))
+    return rc;
+  cew_final_kernel<<<1, kRows, 0, s>>>((const double*)ws, blocks, out2);
   LIDAL_CHECK_LAUNCH("ce_weighted_final");
   return 0;
 }
@@ -692,18 +560,13 @@ extern "C" int lidal_ce_weighted_bwd(const void* logits, int dtype, const int64_
   hipStream_t s = (hipStream_t)stream;
   LIDAL_REQUIRE(c >= 1 && c <= kMaxClasses, "weighted cross_entropy: classes must be in 1..%d", kMaxClasses);
   if (n == 0) return 0;
-  const unsigned nb = (unsigned)cdiv(n, LV_ROWS);
+  const unsigned nb = (unsigned)cdiv(n, kRows);
   const bool vec = aligned16(logits) && aligned16(dlogits);
-  if (dtype == LIDAL_F32)
-    cew_bwd_kernel<float><<<nb, LV_ROWS, 0, s>>>((const float*)logits, labels, n, c, ignore_index, vec, weight, fwd_out2,
-                                                 grad_scale, (float*)dlogits);
-  else if (dtype == LIDAL_BF16)
-    cew_bwd_kernel<__bf16><<<nb, LV_ROWS, 0, s>>>((const __bf16*)logits, labels, n, c, ignore_index, vec, weight, fwd_out2,
-                                                  grad_scale, (__bf16*)dlogits);
-  else {
-    set_error("weighted cross_entropy: bad dtype %d", dtype);
-    return 2;
-  }
-  LIDAL_CHECK_LAUNCH("ce_weighted_bwd");
-  return 0;
+  return with_dtype(dtype, "weighted cross_entropy", [&](auto t) {
+    using T = decltype(t);
+    cew_bwd_kernel<T><<<nb, kRows, 0, s>>>((const T*)logits, labels, n, c, ignore_index, vec, weight, fwd_out2, grad_scale,
+                                           (T*)dlogits);
+    LIDAL_CHECK_LAUNCH("ce_weighted_bwd");
+    return 0;
+  });
 }

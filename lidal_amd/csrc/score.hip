@@ -9,7 +9,7 @@
 
 #include "common.h"
 #include "grid.h"
-#include "npsum.h"
+#include "rows.h"
 
 // The reference computes these quantities with numpy (separately rounded products and sums); hipcc
 // contracts a*b+c into fma even through __dmul_rn/__dadd_rn, so this unit is built with
@@ -18,6 +18,7 @@
 using namespace lidal;
 using namespace lidal::grid;
 using namespace lidal::npsum;
+using lidal::rows::row_exp;
 
 namespace {
 
@@ -33,16 +34,8 @@ __global__ void __launch_bounds__(256) view_mean_softmax_kernel(const float* __r
 #pragma unroll
   for (int j = 0; j < kMaxClasses; ++j) acc[j] = 0.f;
   for (int v = 0; v < reps; ++v) {
-    const float* row = logits + inverse[(int64_t)v * p + i] * c;
-    float x[kMaxClasses];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < kMaxClasses; ++j)
-      if (j < c) { x[j] = row[j]; mx = fmaxf(mx, x[j]); }
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < kMaxClasses; ++j)
-      if (j < c) { x[j] = expf(x[j] - mx); s += x[j]; }
+    float x[kMaxClasses], mx, s;
+    row_exp<float>(logits + inverse[(int64_t)v * p + i] * c, c, x, mx, s);
 #pragma unroll
     for (int j = 0; j < kMaxClasses; ++j)
       if (j < c) acc[j] = (v == 0) ? (x[j] / s) : __fadd_rn(acc[j], x[j] / s);
@@ -61,26 +54,9 @@ __global__ void __launch_bounds__(256) view_mean_softmax_kernel(const float* __r
 }
 
 // ---------------- disagreement of the views ----------------
-// The soft-max of one gathered logits row, view_mean_softmax_kernel's statements: the probability of class j is
-// x[j] / s.  Returns the class of the row's first maximum.  view_scores_kernel reads every row twice through this and
-// gets the same bits both times.
-__device__ __forceinline__ int view_row_softmax(const float* __restrict__ row, int c, float (&x)[kMaxClasses], float& s) {
-  float mx = -INFINITY;
-  int arg = 0;
-#pragma unroll
-  for (int j = 0; j < kMaxClasses; ++j)
-    if (j < c) {
-      x[j] = row[j];
-      if (x[j] > mx) arg = j;
-      mx = fmaxf(mx, x[j]);
-    }
-  s = 0.f;
-#pragma unroll
-  for (int j = 0; j < kMaxClasses; ++j)
-    if (j < c) { x[j] = expf(x[j] - mx); s += x[j]; }
-  return arg;
-}
-
+// The soft-max of a gathered logits row is rows.h's row_exp<float> and a divide by s, view_mean_softmax_kernel's: view_scores_kernel
+// reads every row twice through it and gets the same bits both times.
+//
 // LiDAL.py:59-81 with the point's own view mean m where the query frame stands and its views p_v where the matched
 // neighbours stand: viewd = (1 / reps) sum_v np_sum_f32_k (float)kl_div(m_k + eps, p_vk + eps) in an f64 accumulator,
 // viewe = scipy's entropy(m), agree = the views whose logits row has its first maximum at pred.  prob and pred are
@@ -98,9 +74,8 @@ __global__ void __launch_bounds__(256) view_scores_kernel(const float* __restric
 #pragma unroll
   for (int j = 0; j < kMaxClasses; ++j) m[j] = 0.f;
   for (int v = 0; v < reps; ++v) {
-    float x[kMaxClasses];
-    float s;
-    view_row_softmax(logits + inverse[(int64_t)v * p + i] * c, c, x, s);
+    float x[kMaxClasses], mx, s;
+    row_exp<float>(logits + inverse[(int64_t)v * p + i] * c, c, x, mx, s);
 #pragma unroll
     for (int j = 0; j < kMaxClasses; ++j)
       if (j < c) m[j] = (v == 0) ? (x[j] / s) : __fadd_rn(m[j], x[j] / s);
@@ -120,9 +95,8 @@ __global__ void __launch_bounds__(256) view_scores_kernel(const float* __restric
   double div = 0.0;
   int votes = 0;
   for (int v = 0; v < reps; ++v) {
-    float x[kMaxClasses];
-    float s;
-    votes += (view_row_softmax(logits + inverse[(int64_t)v * p + i] * c, c, x, s) == arg) ? 1 : 0;
+    float x[kMaxClasses], mx, s;
+    votes += (row_exp<float>(logits + inverse[(int64_t)v * p + i] * c, c, x, mx, s) == arg) ? 1 : 0;
     float term[kMaxClasses];
 #pragma unroll
     for (int k = 0; k < kMaxClasses; ++k)

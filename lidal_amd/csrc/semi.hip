@@ -7,18 +7,18 @@
 // without packed-f32 instructions (lidal_amd/build.py); vector stores only, no float atomics: every float sum has one
 // fixed order, so two runs give the same bits.
 //
-// The row softmax everywhere is view_row_softmax of score.hip, restated for f32 and bf16 rows: first maximum,
-// expf(x - mx), running f32 sum in class order, f32 divide.
+// The row softmax everywhere is the view form of rows.h, score.hip's: first maximum, expf(x - mx), running f32 sum in
+// class order, f32 divide.
 #include "multi_tensor.h"
-#include "npsum.h"
+#include "rows.h"
 
 #pragma clang fp contract(off)
 
 namespace lidal {
 namespace {
 
-using npsum::kMaxClasses;
 using npsum::np_sum_f32;
+using namespace rows;
 
 // ---------------------------------------------------------------------------------------------------------- EMA
 // t = t + (s - t) * oma per f32 element (kind 0), or a copy of 32-bit words with no arithmetic on them (kind 1), over the
@@ -71,34 +71,6 @@ __global__ __launch_bounds__(multi_tensor::kThreads) void ema_step_kernel(const 
   });
 }
 
-// ---------------------------------------------------------------------------------------------------------- rows
-template <typename T>
-__device__ __forceinline__ int row_softmax(const T* __restrict__ row, int c, float (&x)[kMaxClasses], float& mx, float& s) {
-  mx = -INFINITY;
-  int arg = 0;
-#pragma unroll
-  for (int j = 0; j < kMaxClasses; ++j)
-    if (j < c) {
-      x[j] = (float)row[j];
-      if (x[j] > mx) arg = j;
-      mx = fmaxf(mx, x[j]);
-    }
-  s = 0.f;
-#pragma unroll
-  for (int j = 0; j < kMaxClasses; ++j)
-    if (j < c) { x[j] = expf(x[j] - mx); s += x[j]; }
-  return arg;
-}
-
-// the value of x[arg] for a run-time arg, without indexing the register array
-__device__ __forceinline__ float pick(const float (&x)[kMaxClasses], int c, int arg) {
-  float v = 0.f;
-#pragma unroll
-  for (int j = 0; j < kMaxClasses; ++j)
-    if (j < c && j == arg) v = x[j];
-  return v;
-}
-
 // ---------------------------------------------------------------------------------------------------------- pseudo labels
 constexpr int PL_THREADS = 256;
 
@@ -123,7 +95,7 @@ __global__ void __launch_bounds__(PL_THREADS) pseudo_labels_kernel(const T* __re
     float conf = 0.f;
     if (in) {
       float x[kMaxClasses], mx, s;
-      arg = row_softmax<T>(logits + row * c, c, x, mx, s);
+      arg = row_exp<float>(logits + row * c, c, x, mx, s);
       conf = pick(x, c, arg) / s;
     }
     int64_t y = ignore_index;
@@ -146,43 +118,7 @@ __global__ void __launch_bounds__(PL_THREADS) pseudo_labels_kernel(const T* __re
 }
 
 // ---------------------------------------------------------------------------------------------------------- consistency
-constexpr int CS_ROWS = 256;
 enum { KIND_MSE = 0, KIND_KL = 1 };
-
-// A workgroup's rows are one contiguous piece of the [n, c] matrix: moved with whole-wave contiguous accesses whatever
-// c is, through an LDS image whose rows are c | 1 words apart (lanes reading their own row do not meet in one bank).
-template <typename T>
-__device__ __forceinline__ void rows_in(const T* __restrict__ src, int64_t row0, int rows, int c, int cs,
-                                        float* __restrict__ lds) {
-  const T* p = src + row0 * c;
-  const int total = rows * c;
-  const int dr = CS_ROWS / c, dc = CS_ROWS % c;         // (row, column) of element q + 256 from those of q: no division per element
-  int r = threadIdx.x / c, k = threadIdx.x % c;
-  for (int q = threadIdx.x; q < total; q += CS_ROWS) {
-    lds[r * cs + k] = (float)p[q];
-    r += dr; k += dc;
-    if (k >= c) { k -= c; ++r; }
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ void rows_out(T* __restrict__ dst, int64_t row0, int rows, int c, int cs,
-                                         const float* __restrict__ lds) {
-  T* p = dst + row0 * c;
-  const int total = rows * c;
-  const int dr = CS_ROWS / c, dc = CS_ROWS % c;
-  int r = threadIdx.x / c, k = threadIdx.x % c;
-  for (int q = threadIdx.x; q < total; q += CS_ROWS) {
-    p[q] = (T)lds[r * cs + k];
-    r += dr; k += dc;
-    if (k >= c) { k -= c; ++r; }
-  }
-}
-
-__device__ __forceinline__ int rows_of_block(int64_t n) {
-  const int64_t left = n - (int64_t)blockIdx.x * CS_ROWS;
-  return left < CS_ROWS ? (left > 0 ? (int)left : 0) : CS_ROWS;
-}
 
 // What both passes know of one row.  Logits: ps / pt the two softmaxes, ls / lt the log-softmaxes (kind 'kl').
 // Probabilities: ps / pt as given.  conf = the teacher's first maximum.
@@ -203,8 +139,8 @@ __device__ __forceinline__ void row_pair(const float (&zs)[kMaxClasses], const f
     return;
   }
   float mxs, ss, mxt, st;
-  row_softmax<float>(zs, c, R.ps, mxs, ss);
-  const int arg = row_softmax<float>(zt, c, R.pt, mxt, st);
+  row_exp<float>(zs, c, R.ps, mxs, ss);
+  const int arg = row_exp<float>(zt, c, R.pt, mxt, st);
   R.conf = pick(R.pt, c, arg) / st;
   const float lss = logf(ss), lst = logf(st);
 #pragma unroll
@@ -218,36 +154,31 @@ __device__ __forceinline__ void row_pair(const float (&zs)[kMaxClasses], const f
 
 // the workgroup's rows of both operands, each thread's own pair into its registers, through ONE LDS image
 template <typename TS, typename TT>
-__device__ __forceinline__ void load_pair(const TS* __restrict__ zs_g, const TT* __restrict__ zt_g, int64_t row0, int nrows,
-                                          int c, int cs, float* __restrict__ rows, float (&zs)[kMaxClasses],
-                                          float (&zt)[kMaxClasses]) {
-  rows_in<TS>(zs_g, row0, nrows, c, cs, rows);
+__device__ __forceinline__ void load_pair(const Tile& tile, const TS* __restrict__ zs_g, const TT* __restrict__ zt_g,
+                                          float (&zs)[kMaxClasses], float (&zt)[kMaxClasses]) {
+  tile.load<TS>(zs_g, false);           // false here, and at the store of dz: the switch to 16-byte vectors
   __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kMaxClasses; ++j) zs[j] = (j < c && (int)threadIdx.x < nrows) ? rows[threadIdx.x * cs + j] : 0.f;
+  tile.own(zs);
   __syncthreads();
-  rows_in<TT>(zt_g, row0, nrows, c, cs, rows);
+  tile.load<TT>(zt_g, false);
   __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kMaxClasses; ++j) zt[j] = (j < c && (int)threadIdx.x < nrows) ? rows[threadIdx.x * cs + j] : 0.f;
+  tile.own(zt);
 }
 
 // r_i (masked) of every row, per_row (optional), and the workgroup's f64 partial in a fixed order
 template <typename TS, typename TT, bool PROBS>
-__global__ void __launch_bounds__(CS_ROWS) consistency_fwd_kernel(const TS* __restrict__ zs, const TT* __restrict__ zt,
-                                                                  int64_t n, int c, int kind, float min_conf,
-                                                                  float* __restrict__ per_row,
-                                                                  double* __restrict__ part) {
-  __shared__ float rows[CS_ROWS * (kMaxClasses + 1)];
-  __shared__ double red[CS_ROWS];
-  const int cs = c | 1;
-  const int64_t row0 = (int64_t)blockIdx.x * CS_ROWS;
-  const int nrows = rows_of_block(n);
+__global__ void __launch_bounds__(kRows) consistency_fwd_kernel(const TS* __restrict__ zs, const TT* __restrict__ zt,
+                                                                int64_t n, int c, int kind, float min_conf,
+                                                                float* __restrict__ per_row,
+                                                                double* __restrict__ part) {
+  __shared__ float lds[kTileFloats];
+  __shared__ double red[1][kRows];
+  const Tile tile(lds, n, c);
   float xs[kMaxClasses], xt[kMaxClasses];
-  load_pair<TS, TT>(zs, zt, row0, nrows, c, cs, rows, xs, xt);
+  load_pair<TS, TT>(tile, zs, zt, xs, xt);
   float r = 0.f;
-  if ((int)threadIdx.x < nrows) {
-    float* mine = rows + threadIdx.x * cs;
+  if ((int)threadIdx.x < tile.nrows) {
+    float* mine = tile.mine();
     RowPair R;
     row_pair<PROBS>(xs, xt, c, kind, R);
     if (R.conf >= min_conf) {                               // (a NaN confidence masks the row)
@@ -263,50 +194,37 @@ __global__ void __launch_bounds__(CS_ROWS) consistency_fwd_kernel(const TS* __re
         }
       r = np_sum_f32(mine, c);                              // (the thread's own LDS row: no one else reads it any more)
     }
-    if (per_row != nullptr) per_row[row0 + threadIdx.x] = r;
+    if (per_row != nullptr) per_row[tile.row0 + threadIdx.x] = r;
   }
-  red[threadIdx.x] = (double)r;
-  __syncthreads();
-  for (int w = CS_ROWS / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+  const double v[1] = {(double)r};
+  block_sum<1>(v, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0][0];
 }
 
 // out2 = {sum / denom, sum}: one workgroup, fixed order
-__global__ void __launch_bounds__(256) consistency_final_kernel(const double* __restrict__ part, int64_t nblocks,
-                                                                double denom, double* __restrict__ out2) {
-  __shared__ double red[256];
-  double a = 0.0;
-  for (int64_t i = threadIdx.x; i < nblocks; i += 256) a += part[i];
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
+__global__ void __launch_bounds__(kRows) consistency_final_kernel(const double* __restrict__ part, int64_t nblocks,
+                                                                  double denom, double* __restrict__ out2) {
+  __shared__ double red[1][kRows];
+  sum_partials<1>(part, nblocks, red);
   if (threadIdx.x == 0) {
-    out2[0] = red[0] / denom;
-    out2[1] = red[0];
+    out2[0] = red[0][0] / denom;
+    out2[1] = red[0][0];
   }
 }
 
 // dz of every row; k1 = the scale of the objective as f32: 1 / (n c) ('mse' on logits), 2 / (n c) ('mse' on
 // probabilities), 1 / n ('kl'); coef = g * k1 is ONE f32 product, and so is every product below.
 template <typename TS, typename TT, bool PROBS>
-__global__ void __launch_bounds__(CS_ROWS) consistency_bwd_kernel(const TS* __restrict__ zs, const TT* __restrict__ zt,
-                                                                  int64_t n, int c, int kind, float min_conf, float k1,
-                                                                  const float* __restrict__ grad_scale,
-                                                                  TS* __restrict__ dz) {
-  __shared__ float rows[CS_ROWS * (kMaxClasses + 1)];
-  const int cs = c | 1;
-  const int64_t row0 = (int64_t)blockIdx.x * CS_ROWS;
-  const int nrows = rows_of_block(n);
+__global__ void __launch_bounds__(kRows) consistency_bwd_kernel(const TS* __restrict__ zs, const TT* __restrict__ zt,
+                                                                int64_t n, int c, int kind, float min_conf, float k1,
+                                                                const float* __restrict__ grad_scale,
+                                                                TS* __restrict__ dz) {
+  __shared__ float lds[kTileFloats];
+  const Tile tile(lds, n, c);
   float xs[kMaxClasses], xt[kMaxClasses];
-  load_pair<TS, TT>(zs, zt, row0, nrows, c, cs, rows, xs, xt);
-  if ((int)threadIdx.x < nrows) {
-    float* mine = rows + threadIdx.x * cs;
+  load_pair<TS, TT>(tile, zs, zt, xs, xt);
+  if ((int)threadIdx.x < tile.nrows) {
+    float* mine = tile.mine();
     const float coef = grad_scale[0] * k1;
     RowPair R;
     row_pair<PROBS>(xs, xt, c, kind, R);
@@ -328,7 +246,7 @@ __global__ void __launch_bounds__(CS_ROWS) consistency_bwd_kernel(const TS* __re
       }
   }
   __syncthreads();
-  rows_out<TS>(dz, row0, nrows, c, cs, rows);
+  tile.store<TS>(dz, false);
 }
 
 int consistency_check(const char* what, int64_t n, int c, int s_dtype, int t_dtype, int kind, int is_probs) {
@@ -350,7 +268,7 @@ struct ConsistencyWs {
 
 ConsistencyWs consistency_layout(void* base, int64_t n) {
   ConsistencyWs w;
-  w.nb = cdiv(n > 0 ? n : 1, CS_ROWS);
+  w.nb = cdiv(n > 0 ? n : 1, kRows);
   Carver cv(base);
   w.part = cv.take<double>(w.nb);
   w.total = cv.total();
@@ -392,16 +310,13 @@ extern "C" int lidal_pseudo_labels(const void* logits, int dtype, int64_t nv, in
   LIDAL_HIP(hipMemsetAsync(stats, 0, (size_t)(c + 2) * 8, s));
   if (p == 0) return 0;
   const unsigned nb = (unsigned)cdiv(p, PL_THREADS);
-  if (dtype == LIDAL_F32)
-    pseudo_labels_kernel<float><<<nb, PL_THREADS, 0, s>>>((const float*)logits, nv, c, thresholds, (float)threshold,
-                                                          inverse, labels, ignore_index, p, out,
-                                                          (unsigned long long*)stats, conf);
-  else
-    pseudo_labels_kernel<__bf16><<<nb, PL_THREADS, 0, s>>>((const __bf16*)logits, nv, c, thresholds, (float)threshold,
-                                                           inverse, labels, ignore_index, p, out,
-                                                           (unsigned long long*)stats, conf);
-  LIDAL_CHECK_LAUNCH("pseudo_labels");
-  return 0;
+  return with_dtype(dtype, "pseudo_labels", [&](auto t) {
+    using T = decltype(t);
+    pseudo_labels_kernel<T><<<nb, PL_THREADS, 0, s>>>((const T*)logits, nv, c, thresholds, (float)threshold, inverse,
+                                                      labels, ignore_index, p, out, (unsigned long long*)stats, conf);
+    LIDAL_CHECK_LAUNCH("pseudo_labels");
+    return 0;
+  });
 }
 
 extern "C" int64_t lidal_consistency_workspace_bytes(int64_t n) {
@@ -422,7 +337,7 @@ extern "C" int lidal_consistency_fwd(const void* student, int s_dtype, const voi
   const unsigned nb = (unsigned)w.nb;
   const float mc = (float)min_conf;
 #define LIDAL_CS_FWD(TS, TT, P) \
-  consistency_fwd_kernel<TS, TT, P><<<nb, CS_ROWS, 0, s>>>((const TS*)student, (const TT*)teacher, n, c, kind, mc, per_row, w.part)
+  consistency_fwd_kernel<TS, TT, P><<<nb, kRows, 0, s>>>((const TS*)student, (const TT*)teacher, n, c, kind, mc, per_row, w.part)
   if (is_probs) LIDAL_CS_FWD(float, float, true);
   else if (s_dtype == LIDAL_F32 && t_dtype == LIDAL_F32) LIDAL_CS_FWD(float, float, false);
   else if (s_dtype == LIDAL_F32) LIDAL_CS_FWD(float, __bf16, false);
@@ -443,12 +358,12 @@ extern "C" int lidal_consistency_bwd(const void* student, int s_dtype, const voi
   if (int rc = consistency_check("consistency_bwd", n, c, s_dtype, t_dtype, kind, is_probs)) return rc;
   LIDAL_REQUIRE(n > 0 && student != nullptr && teacher != nullptr && grad_scale != nullptr && dz != nullptr,
                 "consistency_bwd: no rows or a null operand");
-  const unsigned nb = (unsigned)cdiv(n, CS_ROWS);
+  const unsigned nb = (unsigned)cdiv(n, kRows);
   const float mc = (float)min_conf;
   const double nd = (double)n;
   const float k1 = kind == KIND_KL ? (float)(1.0 / nd) : (float)((is_probs ? 2.0 : 1.0) / (nd * (double)c));
 #define LIDAL_CS_BWD(TS, TT, P) \
-  consistency_bwd_kernel<TS, TT, P><<<nb, CS_ROWS, 0, s>>>((const TS*)student, (const TT*)teacher, n, c, kind, mc, k1, grad_scale, (TS*)dz)
+  consistency_bwd_kernel<TS, TT, P><<<nb, kRows, 0, s>>>((const TS*)student, (const TT*)teacher, n, c, kind, mc, k1, grad_scale, (TS*)dz)
   if (is_probs) LIDAL_CS_BWD(float, float, true);
   else if (s_dtype == LIDAL_F32 && t_dtype == LIDAL_F32) LIDAL_CS_BWD(float, float, false);
   else if (s_dtype == LIDAL_F32) LIDAL_CS_BWD(float, __bf16, false);

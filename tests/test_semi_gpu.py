@@ -497,6 +497,65 @@ def test_on_probabilities_everything_equals_the_restatement_bit_for_bit(n, c):
         assert float(loss) == float(np.float32(float(out2[0])))
 
 
+@pytest.mark.parametrize('c', [1, 2, 19, 32])
+def test_one_softmax_across_the_units(c):
+    """csrc/rows.h holds the one row softmax: P = view_mean_softmax of one view through the identity (score.hip) is the
+    softmax pseudo_labels and the consistency term (semi.hip) take of the same logits.  So conf is P.max(1) bit for bit
+    and the accepted labels are pred; and the 'mse' term on logits equals the one on P(zs), P(zt) bit for bit in out2 and
+    per_row, unmasked and under a min_conf that masks some rows."""
+    from lidal_amd import semi
+    from lidal_amd.score.prob_inference import view_mean_softmax
+    n = 257
+    zs, zt = (_g(z) for z in consistency_case(n, c, 'f32'))
+    ident = torch.arange(n, device=DEV)
+    (ps, _), (pt, pred) = view_mean_softmax(zs, ident, 1), view_mean_softmax(zt, ident, 1)
+    top = pt.max(1).values
+    thr = float(top.median()) if c > 1 else 1.0
+    labels, stats, conf = semi.pseudo_labels(zt, thr, return_conf=True)
+    assert torch.equal(conf.view(torch.int32), top.view(torch.int32))
+    took = labels != 255
+    assert int(took.sum()) == int(stats[:c].sum()) > 0 and torch.equal(labels[took], pred[took])
+    if c > 1:
+        assert int(stats[c]) > 0                        # and some were rejected
+    for mc in (0.0, thr if c > 1 else 2.0):
+        a2, a_rows = semi.consistency_forward(zs, zt, 'mse', mc, probs=False, per_row=True)
+        b2, b_rows = semi.consistency_forward(ps, pt, 'mse', mc, probs=True, per_row=True)
+        assert torch.equal(a2.view(torch.int64), b2.view(torch.int64))
+        assert torch.equal(a_rows.view(torch.int32), b_rows.view(torch.int32))
+        assert mc == 0.0 or int((top < mc).sum()) > 0
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+def test_consistency_operands_off_the_16_byte_grid_give_the_same_bits(dtype):
+    """`x[1:]` of a [258, 19] matrix starts 76 (f32) or 38 (bf16) bytes into its allocation.  The consistency kernels
+    move their rows by elements wherever they start: forward and backward equal those on aligned copies bit for bit,
+    both kinds, and the row in front of each view is not touched (tests/test_loss_gpu.py holds the losses to the same)."""
+    from lidal_amd import semi
+    n, c = 257, 19
+    wholes = []
+    for z in consistency_case(n, c, 'f32'):
+        whole = torch.full((n + 1, c), 7.0, device=DEV).to(dtype)
+        whole[1:] = _g(z).to(dtype)
+        wholes.append(whole)
+
+    def run(s, t, kind):
+        s = s.detach().requires_grad_(True)             # (a leaf on the same storage)
+        loss, rows = semi.consistency_loss(s, t, kind=kind, per_row=True)
+        (loss * 1.5).backward()
+        out2, _ = semi.consistency_forward(s.detach(), t, kind)
+        return out2, loss.detach(), rows, s.grad
+
+    for kind in R.KINDS:
+        views = [w[1:].detach() for w in wholes]
+        assert all(v.data_ptr() % 16 != 0 and v.is_contiguous() for v in views)
+        got = run(views[0], views[1], kind)
+        want = run(views[0].clone(), views[1].clone(), kind)
+        for a, b in zip(got, want):
+            assert torch.equal(a, b)
+        assert float(want[0][1]) != 0.0 and bool(want[3].any())
+    assert all(bool((w[0] == 7.0).all()) for w in wholes)
+
+
 def test_forward_scratch_is_exactly_what_the_library_says(monkeypatch):
     from lidal_amd import backend as B
     from lidal_amd import semi
