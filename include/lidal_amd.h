@@ -697,6 +697,44 @@ int lidal_interframe_score_ordered(const double* q_pts, const float* q_prob, int
                                    int n_nei, double dis_thresh, double* interd, float* intere,
                                    int32_t* map_count, void* ws, int64_t ws_bytes, const void* q_grid,
                                    void* stream);
+/* ---- labels and predictions carried across registered frames (csrc/transfer.hip) ---------- */
+/* Stage 1 of lidal_interframe_score as an entry point of its own (the same kernel): match i32 [n_nei][p], caller's
+ * buffer of n_nei * p entries; match[n][i] = the nearest point of neighbour n to query i with sqrt(d2) <= dis_thresh
+ * (d2 = ((ex*ex + ey*ey) + ez*ez) in f64, ties to the lowest index), or -1.  A neighbour with p_n <= 0 gives a row of
+ * -1; a query that is NaN, infinite or out of range matches nothing (lidal_nn_grid_build).  The host arrays are those
+ * of lidal_interframe_score.  n_nei in 0..32; p == 0 or n_nei == 0 writes nothing and returns 0. */
+int lidal_interframe_match(const double* q_pts, int64_t p, const void* const* nei_grids_host,
+                           const double* const* nei_pts_host, const int64_t* nei_p_host, int n_nei,
+                           double dis_thresh, int32_t* match, void* stream);
+/* Stage 2 for labels and predictions: one thread per query point walks match[0..n_nei)[i] in order.  An entry outside
+ * [0, nei_p_host[n]) is no match.  Two output groups; a group is off when ALL of its pointers are NULL, at least one
+ * must be on, and a group of which only some pointers are given is refused.
+ *   Annotation group: nei_labels_host (host array of device i64*, one per neighbour; a NULL entry votes nothing),
+ *   q_labels i64 [p] or NULL, gate i64 [p] or NULL -> out i64 [p], votes i32 [p], agree i32 [p], stats i64 [c + 7].
+ *     For neighbour n with j = match[n][i] matched and l = nei_labels[n][j]: l == ignore_index is skipped, l outside
+ *     [0, c) is skipped and counted invalid, otherwise hist[l]++, nv++.  winner = the FIRST maximum of hist,
+ *     ag = hist[winner]; votes[i] = nv, agree[i] = ag.  out[i] by the first rule that applies:
+ *       1. q_labels[i], when given and != ignore_index                                           (own; and when rules
+ *          2-4 would have let the vote through: confirmed if winner == q_labels[i], else contradicted)
+ *       2. ignore_index when nv == 0                                                             (none)
+ *       3. ignore_index when nv < min_votes or (double)ag < min_agree * (double)nv               (weak)
+ *       4. ignore_index when gate is given and gate[i] != winner                                 (gated)
+ *       5. winner                                                                                (stats[winner])
+ *     stats = the c class counts, then own, none, weak, gated, confirmed, contradicted, invalid; zeroed by this call,
+ *     integer atomics only, never read back here.
+ *   Prediction group: q_prob f32 [p,c], nei_prob_host (as lidal_interframe_score) -> fused_prob f32 [p,c],
+ *   fused_pred i64 [p], fused_conf f32 [p], count i32 [p].
+ *     sum_k = q_prob[i][k]; per matched neighbour in order sum_k = fl32(sum_k + nei_prob[n][j][k]);
+ *     fused_prob[i][k] = (float)((double)sum_k / (double)(count + 1)) -- the mean row whose entropy is
+ *     lidal_interframe_score's intere; fused_pred = its first maximum, fused_conf that entry.
+ * c in 1..32, n_nei in 0..32, min_votes >= 1, 0 < min_agree <= 1 (whichever group is on); p == 0 returns 0.  No workspace,
+ * no float atomics: every output is a function of the inputs alone. */
+int lidal_interframe_transfer(const int32_t* match, int64_t p, int c, int n_nei, const int64_t* nei_p_host,
+                              const int64_t* const* nei_labels_host, const int64_t* q_labels, const int64_t* gate,
+                              int64_t ignore_index, int min_votes, double min_agree, int64_t* out, int32_t* votes,
+                              int32_t* agree, int64_t* stats, const float* q_prob,
+                              const float* const* nei_prob_host, float* fused_prob, int64_t* fused_pred,
+                              float* fused_conf, int32_t* count, void* stream);
 /* replaces score/sv_level/LiDAL.py:91-98: per-supervoxel means over point lists given as CSR
  * (sv_ptr i64 [s+1], sv_idx i64 [sv_ptr[s]]).  sv_interd f32 [s], sv_intere f32 [s],
  * sv_center f32 [s,3]. */

@@ -152,6 +152,9 @@ SIGNATURES = {
                                       _vp, _vp, _vp, _i64, _vp]),
     'lidal_interframe_score_ordered': (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _f64, _vp,
                                               _vp, _vp, _vp, _i64, _vp, _vp]),
+    'lidal_interframe_match': (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _f64, _vp, _vp]),
+    'lidal_interframe_transfer': (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lidal_supervoxel_reduce': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     'lidal_radius_pairs_workspace_bytes': (_i64, [_i64]),
     'lidal_radius_pairs_count': (_i32, [_vp, _i64, _f32, _vp, _vp, _vp, _i64, _vp]),

@@ -495,6 +495,22 @@ extern "C" int64_t lidal_interframe_workspace_bytes(int64_t p, int n_nei) {
   return (int64_t)(n_nei > 0 ? n_nei : 1) * (p > 0 ? p : 1) * 4 + 256;
 }
 
+// the neighbour frames of a query frame as the kernels take them (nei_prob_host NULL: the match stage reads none)
+static NeiArgs nei_args(const void* const* nei_grids_host, const double* const* nei_pts_host,
+                        const float* const* nei_prob_host, const int64_t* nei_p_host, int n_nei) {
+  NeiArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n_nei;
+  for (int n = 0; n < n_nei; ++n) {
+    a.grid[n] = nei_grids_host[n];
+    a.pts[n] = nei_pts_host[n];
+    a.prob[n] = nei_prob_host != nullptr ? nei_prob_host[n] : nullptr;
+    a.p[n] = nei_p_host[n];
+    a.cap[n] = grid_cap(nei_p_host[n] > 0 ? nei_p_host[n] : 1);
+  }
+  return a;
+}
+
 static int interframe_score(const double* q_pts, const float* q_prob, int64_t p, int c,
                             const void* const* nei_grids_host, const double* const* nei_pts_host,
                             const float* const* nei_prob_host, const int64_t* nei_p_host,
@@ -506,16 +522,7 @@ static int interframe_score(const double* q_pts, const float* q_prob, int64_t p,
   if (p == 0) return 0;
   LIDAL_REQUIRE(ws_bytes >= lidal_interframe_workspace_bytes(p, n_nei), "interframe workspace too small");
   int* match = (int*)ws;
-  NeiArgs a;
-  memset(&a, 0, sizeof(a));
-  a.n = n_nei;
-  for (int n = 0; n < n_nei; ++n) {
-    a.grid[n] = nei_grids_host[n];
-    a.pts[n] = nei_pts_host[n];
-    a.prob[n] = nei_prob_host[n];
-    a.p[n] = nei_p_host[n];
-    a.cap[n] = grid_cap(nei_p_host[n] > 0 ? nei_p_host[n] : 1);
-  }
+  const NeiArgs a = nei_args(nei_grids_host, nei_pts_host, nei_prob_host, nei_p_host, n_nei);
   hipStream_t s = (hipStream_t)stream;
   // the query frame's points in cell order: the sorted ids inside its own grid buffer (lidal_nn_grid_build of q_pts)
   const int* q_order = nullptr;
@@ -531,6 +538,25 @@ static int interframe_score(const double* q_pts, const float* q_prob, int64_t p,
   interframe_kernel<<<(unsigned)cdiv(p, 256), 256, 0, s>>>(q_prob, p, c, a, match, interd, intere,
                                                            map_count, q_order);
   LIDAL_CHECK_LAUNCH("lidal_interframe_score");
+  return 0;
+}
+
+// Stage 1 alone: the match table of lidal_interframe_score, kept by the caller.
+extern "C" int lidal_interframe_match(const double* q_pts, int64_t p, const void* const* nei_grids_host,
+                                      const double* const* nei_pts_host, const int64_t* nei_p_host, int n_nei,
+                                      double dis_thresh, int32_t* match, void* stream) {
+  LIDAL_REQUIRE(n_nei >= 0 && n_nei <= MAXNEI, "interframe_match: at most %d neighbours", MAXNEI);
+  LIDAL_REQUIRE(p >= 0, "interframe_match: p must not be negative");
+  if (p == 0 || n_nei == 0) return 0;
+  LIDAL_REQUIRE(q_pts != nullptr && match != nullptr && nei_grids_host != nullptr && nei_pts_host != nullptr &&
+                    nei_p_host != nullptr, "interframe_match: a NULL argument");
+  for (int n = 0; n < n_nei; ++n)
+    LIDAL_REQUIRE(nei_p_host[n] <= 0 || (nei_grids_host[n] != nullptr && nei_pts_host[n] != nullptr),
+                  "interframe_match: neighbour %d has points but no grid", n);
+  const NeiArgs a = nei_args(nei_grids_host, nei_pts_host, nullptr, nei_p_host, n_nei);
+  interframe_match_kernel<<<dim3((unsigned)cdiv(p, 256), (unsigned)n_nei), 256, 0, (hipStream_t)stream>>>(
+      q_pts, p, a, dis_thresh, match, nullptr);
+  LIDAL_CHECK_LAUNCH("lidal_interframe_match");
   return 0;
 }
 

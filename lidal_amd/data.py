@@ -368,22 +368,43 @@ def val_batch(scans, raw_labels, label_map, rng=np.random):
     return batch
 
 
-def train_batch(scans, raw_labels, label_map, sv_csrs=None, sv_flags=None, pseudos=None, rng=np.random, check=True):
+def _fill_extra(labels_p, extra_labels, what):
+    """labels_p per scan with extra_labels[j] (i64 [P_j] or None: transfer_labels of score/transfer.py) where
+    train_labels left `ignore` (255)."""
+    if extra_labels is None:
+        return labels_p
+    out = []
+    for j, (lab, extra) in enumerate(zip(labels_p, extra_labels)):
+        if extra is not None:
+            if not isinstance(extra, torch.Tensor):
+                raise TypeError('%s: extra_labels[%d] must be a tensor or None' % (what, j))
+            if extra.dtype != torch.int64 or extra.shape != lab.shape:
+                raise ValueError('%s: extra_labels[%d] must be int64 [%d]' % (what, j, lab.shape[0]))
+            B.require_gpu(extra)
+            lab = torch.where(lab == 255, extra, lab)
+        out.append(lab)
+    return out
+
+
+def train_batch(scans, raw_labels, label_map, sv_csrs=None, sv_flags=None, pseudos=None, rng=np.random, check=True,
+                extra_labels=None):
     """The reference's training batch (modes 'train', 'train_sv', 'train_sv_pseudo' + collate_fn): scans is a list of
     (points, intensity) GPU pairs; raw_labels, sv_csrs, sv_flags and pseudos hold one entry per scan, as train_labels
     takes them.  Draws per scan in order, one voxelize_batch, train_labels per scan for labels_p (no read-back),
     labels_v_b = labels_p_b[unique_idxs_b], one check_labels for the batch (check=False: the counters stay in
-    'labels_invalid') -> the batch of train_step."""
+    'labels_invalid') -> the batch of train_step.  extra_labels: one i64 [P] tensor or None per scan (labels carried over
+    from neighbour frames, score.transfer_labels); it fills labels_p where train_labels left 255, before labels_v_b is
+    taken."""
     if (sv_csrs is None) != (sv_flags is None):
         raise ValueError('train_batch: sv_csrs and sv_flags come together')
     scans = _batch_scans(scans, [('label arrays', raw_labels), ('supervoxel lists', sv_csrs), ('flag arrays', sv_flags),
-                                 ('pseudo label arrays', pseudos)], 'train_batch')
+                                 ('pseudo label arrays', pseudos), ('extra label arrays', extra_labels)], 'train_batch')
     draws = [draw_augmentation(rng) for _ in scans]
     batch = voxelize_batch([x for x, _ in scans], [w for _, w in scans], [d[0] for d in draws], [d[1] for d in draws])
     out = [train_labels(raw_labels[j], label_map, sv_csrs[j] if sv_csrs is not None else None,
                         sv_flags[j] if sv_flags is not None else None, pseudos[j] if pseudos is not None else None,
                         check=False) for j in range(len(scans))]
-    batch['labels_p_b'] = torch.cat([o[0] for o in out])
+    batch['labels_p_b'] = torch.cat(_fill_extra([o[0] for o in out], extra_labels, 'train_batch'))
     batch['labels_v_b'] = batch['labels_p_b'][batch['unique_idxs_b']]
     if check:
         check_labels([o[2] for o in out])
@@ -614,24 +635,27 @@ def mix_scans(points, intensity, labels, mixes):
 
 
 def mixed_train_batch(scans, raw_labels, label_map, mixes, sv_csrs=None, sv_flags=None, pseudos=None, rng=np.random,
-                      check=True):
+                      check=True, extra_labels=None):
     """train_batch over mixed samples: scans, raw_labels, sv_csrs, sv_flags and pseudos as train_batch takes them, and
     one Mix per sample of the batch.  train_labels per scan (no read-back), mix_scans of the scans and their labels_p,
     ONE draw_augmentation(rng) per mix in order, voxelize_batch over the mixed samples, labels_v_b = the mixed
     labels[unique_idxs_b], one check_labels (check=False: the counters stay in 'labels_invalid') -> the batch of
     train_step.  Beside it: labels_p_b and src_p_b per mixed point, src_b per voxel (rows of the concatenated input list:
     any per-point array of the scans follows the batch with array[src]) and parts of mix_scans.  Two read-backs: the
-    mix's row counts and the batch's voxel counts.  identity_mix(j) for every scan gives train_batch's batch."""
+    mix's row counts and the batch's voxel counts.  identity_mix(j) for every scan gives train_batch's batch.
+    extra_labels as train_batch takes them: they fill the scans' labels_p before the scans are mixed."""
     if (sv_csrs is None) != (sv_flags is None):
         raise ValueError('mixed_train_batch: sv_csrs and sv_flags come together')
     scans = _batch_scans(scans, [('label arrays', raw_labels), ('supervoxel lists', sv_csrs), ('flag arrays', sv_flags),
-                                 ('pseudo label arrays', pseudos)], 'mixed_train_batch')
+                                 ('pseudo label arrays', pseudos), ('extra label arrays', extra_labels)],
+                        'mixed_train_batch')
     mixes = list(mixes)
     _mix_arguments([x.shape[0] for x, _ in scans], mixes, True)         # refused before anything is launched
     out = [train_labels(raw_labels[j], label_map, sv_csrs[j] if sv_csrs is not None else None,
                         sv_flags[j] if sv_flags is not None else None, pseudos[j] if pseudos is not None else None,
                         check=False) for j in range(len(scans))]
-    mixed = mix_scans([x for x, _ in scans], [w for _, w in scans], [o[0] for o in out], mixes)
+    mixed = mix_scans([x for x, _ in scans], [w for _, w in scans],
+                      _fill_extra([o[0] for o in out], extra_labels, 'mixed_train_batch'), mixes)
     draws = [draw_augmentation(rng) for _ in mixes]
     ptr = mixed['point_ptr']
     cut = [(int(ptr[j]), int(ptr[j + 1])) for j in range(len(mixes))]

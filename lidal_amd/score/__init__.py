@@ -3,7 +3,8 @@ view-mean probabilities) and score/sv_level/LiDAL.py (inter-frame divergence / e
 supervoxel + greedy selection), with frames sharded over the GPUs of a node; and the ReDAL baseline
 (score/sv_level/ReDAL.py: surface variation, region scores, k-means, diversity-aware selection) on one GPU; and the
 frame-level baselines (score/frame_level/: entropy, margin, confidence, segment entropy, core-set, random); and, beyond
-the reference, the disagreement of a frame's own augmented views per supervoxel and per frame (view_level.py)."""
+the reference, the disagreement of a frame's own augmented views per supervoxel and per frame (view_level.py), and
+annotations and predictions carried across the registered frames of a sequence (transfer.py)."""
 from .frame_level import (FrameBoard, coreset, frame_feature, frame_sequence, frame_uncertainty, random_frames,
                           segment_entropy, select_frames)
 from .interframe import FrameBank, neighbour_ids, score_frame
@@ -13,6 +14,7 @@ from .redal import (RegionBoard, kmeans, knn, redal_sequence, region_scores, sel
                     surface_variation)
 from .selection import centre_pairs, select, select_indexed
 from .sharding import HaloExchange, frame_range, gather_frames, needed_frames
+from .transfer import fuse_predictions, match_points, transfer_labels, transfer_sequence
 from .view_level import frame_view_scores, score_frame_views, view_sequence
 
 __all__ = ['infer_frame', 'FrameBank', 'neighbour_ids', 'score_frame', 'score_sequence', 'collect_sequence', 'ScoreBoard', 'select',
@@ -20,4 +22,5 @@ __all__ = ['infer_frame', 'FrameBank', 'neighbour_ids', 'score_frame', 'score_se
            'frame_range', 'gather_frames', 'needed_frames', 'HaloExchange',
            'surface_variation', 'knn', 'region_scores', 'kmeans', 'select_redal', 'RegionBoard', 'redal_sequence',
            'frame_uncertainty', 'segment_entropy', 'frame_feature', 'coreset', 'select_frames', 'random_frames',
-           'frame_sequence', 'FrameBoard', 'score_frame_views', 'frame_view_scores', 'view_sequence']
+           'frame_sequence', 'FrameBoard', 'score_frame_views', 'frame_view_scores', 'view_sequence',
+           'match_points', 'transfer_labels', 'fuse_predictions', 'transfer_sequence']

@@ -55,14 +55,16 @@ class FrameBank:
     def __len__(self):
         return self.n_frames if self.n_frames is not None else len(self.world)
 
-    def add(self, world, prob, frame_id=None):
+    def add(self, world, prob=None, frame_id=None):
+        """prob None: a frame of geometry alone (round 0 has no model).  It can be matched and can carry labels
+        (score/transfer.py); scoring it, or fusing predictions over it, raises."""
         B.require_gpu(world, prob)
         assert world.dtype == torch.float64 and world.shape[1] == 3
-        assert prob.dtype == torch.float32 and prob.shape[0] == world.shape[0]
+        assert prob is None or (prob.dtype == torch.float32 and prob.shape[0] == world.shape[0])
         f = len(self.world) if frame_id is None else int(frame_id)
         assert f not in self.world
         self.world[f] = world.contiguous()
-        self.prob[f] = prob.contiguous()
+        self.prob[f] = prob.contiguous() if prob is not None else None
         self._grid[f] = None
 
     def grid(self, i):
@@ -87,6 +89,9 @@ def _ptr_array(ctype, tensors):
 def score_points(bank, i, nei_num=24):
     """Per-point (interd f64 [P], intere f32 [P], map_count i32 [P]) of frame i."""
     nei = neighbour_ids(i, len(bank), nei_num)
+    for f in [i] + nei:
+        if bank.prob[f] is None:
+            raise ValueError('score_points: frame %d was added without probabilities (FrameBank.add(world, prob))' % f)
     q_pts, q_prob = bank.world[i], bank.prob[i]
     p, c = q_prob.shape
     dev = q_pts.device
