@@ -735,6 +735,69 @@ int lidal_interframe_transfer(const int32_t* match, int64_t p, int c, int n_nei,
                               int32_t* agree, int64_t* stats, const float* q_prob,
                               const float* const* nei_prob_host, float* fused_prob, int64_t* fused_pred,
                               float* fused_conf, int32_t* count, void* stream);
+/* ---- scan-to-scan registration by point-to-plane ICP (csrc/icp.hip) ------------------------- */
+/* Normals of a raw scan xyz f32 [p,3]: normals f64 [p,3].  Per point: its k nearest OTHER points as lidal_knn orders
+ * them (f64 distance, then index), their population covariance in f64 (mean summed in that order times 1 / k, then the
+ * six second moments about it times 1 / k), cyclic Jacobi with eigenvectors (csrc/sym3.h).  The normal is the
+ * eigenvector (column) of the smallest eigenvalue exactly as the Jacobi leaves it, the lowest column on a tie, negated
+ * when ((nx*x + ny*y) + nz*z) > 0 so that it faces the sensor origin.  (0,0,0) is written when the unclipped surface
+ * variation lambda_min / ((l1 + l2) + l3) exceeds max_variation, when the eigenvalue sum is 0, or when anything is not
+ * finite.  1 <= k <= 64; p < k + 1 is refused (status 2), as by lidal_knn, whose precondition (finite coordinates) and
+ * `cell` are this call's too.  Workspace: lidal_point_normals_workspace_bytes(p, k) = the k-NN table + lidal_knn's own. */
+int64_t lidal_point_normals_workspace_bytes(int64_t p, int k);
+int lidal_point_normals(const float* xyz, int64_t p, int k, double cell, double max_variation, double* normals,
+                        void* ws, int64_t ws_bytes, void* stream);
+/* n_iters iterations of point-to-plane ICP of a source scan onto a target, two launches each, nothing read back.
+ *   src f32 [p_src,3] in the sensor frame; thread t takes source point t * stride (stride >= 1);
+ *   tgt_grid = lidal_nn_grid_build of tgt_pts f64 [p_tgt,3] (any cell: the answers do not depend on it), tgt_normals
+ *   f64 [p_tgt,3] (lidal_point_normals; a (0,0,0) row takes no part);
+ *   pose f64 [16] row-major 4x4 on the device, IN PLACE: the initial estimate in, the result out;
+ *   max_dist_host f64 [n_iters] (host): the match radius of every iteration; consecutive equal values are one LEVEL;
+ *   trace f64 [n_iters][LIDAL_ICP_TRACE] on the device, one row per iteration (below).
+ * ACCUMULATE, per source point: s = pose * src_i in f64, ((h0*P[j][0] + h1*P[j][1]) + h2*P[j][2]) + P[j][3] as
+ * lidal_register_points; j = the nearest target point with sqrt(d2) <= max_dist (lidal_interframe_match's rule, ties to
+ * the lowest index).  No match, a (0,0,0) normal or a non-finite s: the point is skipped.  Else with n the normal and
+ * t = tgt_pts[j]:  r = ((sx-tx)*nx + (sy-ty)*ny) + (sz-tz)*nz;  a = s x n = (sy*nz - sz*ny, sz*nx - sx*nz, sx*ny - sy*nx);
+ * J = (a, n).  The point adds 29 terms: J_u*J_v for u <= v (row-major upper triangle, 21), -(J_u*r) (6), r*r, 1.  Every
+ * product is rounded on its own.  Sums in f64: per thread over its points (t, t + T, t + 2 T, ... with T the threads of
+ * the launch), a fixed tree over the 256 threads of a workgroup, one partial row per workgroup; the number of
+ * workgroups is min(ceil(ceil(p_src / stride) / 256), 1024), a function of p_src and stride alone.
+ * FINISH, one workgroup: the partial rows summed in index order; A xi = b with A the symmetric 6x6 of the 21 sums and b
+ * the 6, by Cholesky: for j = 0..5: d = A[j][j] - L[j][0]^2 - ... - L[j][j-1]^2 (left to right), L[j][j] = sqrt(d),
+ * L[i][j] = (A[i][j] - L[i][0]*L[j][0] - ...) / L[j][j]; y[i] = (b[i] - L[i][0]*y[0] - ...) / L[i][i]; xi[i] = (y[i] -
+ * L[i+1][i]*xi[i+1] - ... - L[5][i]*xi[5]) / L[i][i] for i = 5..0.  xi = (omega, v).  q = (1, omega/2) divided by
+ * sqrt(((1 + qx^2) + qy^2) + qz^2); R = the quaternion's rotation matrix (R00 = 1 - 2*(yy + zz), R01 = 2*(xy - wz),
+ * R02 = 2*(xz + wy), R10 = 2*(xy + wz), R11 = 1 - 2*(xx + zz), R12 = 2*(yz - wx), R20 = 2*(xz - wy), R21 = 2*(yz + wx),
+ * R22 = 1 - 2*(xx + yy)); pose <- [R | v; 0 0 0 1] * pose, rows 0..2: ((R[i][0]*P[0][j] + R[i][1]*P[1][j]) +
+ * R[i][2]*P[2][j]) + v[i]*P[3][j].  Only + - * / and sqrt.
+ * STOPPING, on the device: when max|omega| < eps_rot and max|v| < eps_trans the iteration is CONVERGED and the remaining
+ * iterations of its level return at once (SKIPPED).  Fewer than min_pairs pairs (FEW_PAIRS; p_src == 0 is that), or a
+ * Cholesky pivot d that is <= 1e-12 * max_k A[k][k] or not finite (DEGENERATE): the pose stays as the iteration found
+ * it and every later iteration is a no-op (AFTER_FAILURE).
+ * Refused before any launch (status 2): stride < 1, n_iters outside 1..256, a max_dist that is not finite and positive,
+ * min_pairs < 6, NULL pointers (src may be NULL when p_src == 0; tgt_pts and tgt_normals when p_tgt == 0).
+ * Workspace: lidal_icp_workspace_bytes(p_src, stride). */
+enum {
+  LIDAL_ICP_TRACE = 64,            /* doubles per trace row: */
+  LIDAL_ICP_TRACE_SUMS = 0,        /*   the 29 sums (zeros in a SKIPPED / AFTER_FAILURE row); [28] is the pair count */
+  LIDAL_ICP_TRACE_XI = 29,         /*   xi (zeros unless the pose was updated) */
+  LIDAL_ICP_TRACE_STATUS = 35,     /*   one of LIDAL_ICP_* below */
+  LIDAL_ICP_TRACE_MAX_DIST = 36,   /*   the iteration's match radius */
+  LIDAL_ICP_TRACE_POSE = 37        /*   the 16 entries of the pose the iteration started from; [53..63] are 0 */
+};
+enum {
+  LIDAL_ICP_OK = 0,                /* the pose was updated */
+  LIDAL_ICP_CONVERGED = 1,         /* updated, and the update was below eps_rot and eps_trans */
+  LIDAL_ICP_SKIPPED = 2,           /* an earlier iteration of the level converged */
+  LIDAL_ICP_FEW_PAIRS = 3,
+  LIDAL_ICP_DEGENERATE = 4,
+  LIDAL_ICP_AFTER_FAILURE = 5
+};
+int64_t lidal_icp_workspace_bytes(int64_t p_src, int64_t stride);
+int lidal_icp_run(const float* src, int64_t p_src, int64_t stride, const void* tgt_grid, const double* tgt_pts,
+                  const double* tgt_normals, int64_t p_tgt, double* pose, const double* max_dist_host, int n_iters,
+                  int min_pairs, double eps_rot, double eps_trans, double* trace, void* ws, int64_t ws_bytes,
+                  void* stream);
 /* replaces score/sv_level/LiDAL.py:91-98: per-supervoxel means over point lists given as CSR
  * (sv_ptr i64 [s+1], sv_idx i64 [sv_ptr[s]]).  sv_interd f32 [s], sv_intere f32 [s],
  * sv_center f32 [s,3]. */

@@ -155,6 +155,10 @@ SIGNATURES = {
     'lidal_interframe_match': (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _f64, _vp, _vp]),
     'lidal_interframe_transfer': (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lidal_point_normals_workspace_bytes': (_i64, [_i64, _i32]),
+    'lidal_point_normals': (_i32, [_vp, _i64, _i32, _f64, _f64, _vp, _vp, _i64, _vp]),
+    'lidal_icp_workspace_bytes': (_i64, [_i64, _i64]),
+    'lidal_icp_run': (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _f64, _f64, _vp, _vp, _i64, _vp]),
     'lidal_supervoxel_reduce': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     'lidal_radius_pairs_workspace_bytes': (_i64, [_i64]),
     'lidal_radius_pairs_count': (_i32, [_vp, _i64, _f32, _vp, _vp, _vp, _i64, _vp]),

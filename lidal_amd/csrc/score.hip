@@ -171,23 +171,6 @@ __global__ void __launch_bounds__(256) register_kernel(const float* __restrict__
 // ---------------- uniform grid for radius-limited nearest neighbour ----------------
 static inline int64_t grid_cap(int64_t p) { return table_capacity(p); }
 
-static inline GridView grid_view(const void* grid, int64_t p, int64_t cap, double cell) {
-  GridView g;
-  char* base = (char*)grid + 64;
-  g.t.keys = (unsigned long long*)base;
-  g.t.vals = (int*)(base + cap * 8);
-  g.t.mask = (uint64_t)cap - 1;
-  const int64_t q = p > 0 ? p : 1;
-  g.t.bits = (unsigned*)(base + grid_off_bits(cap, q));
-  g.t.sbits = nullptr; g.t.hdr = nullptr;
-  g.keys = (const uint64_t*)(base + grid_off_skeys(cap));
-  g.idx = (const int*)(base + grid_off_sidx(cap, q));
-  g.rec = (const GridRec*)(base + grid_off_spts(cap, q));
-  g.p = p;
-  g.cell = cell;
-  return g;
-}
-
 __global__ void __launch_bounds__(256) grid_keys_kernel(const double* __restrict__ pts, int64_t p,
                                                         double cell, uint64_t* __restrict__ keys,
                                                         int* __restrict__ idx, GridHeader* __restrict__ hdr) {
@@ -226,57 +209,7 @@ __global__ void __launch_bounds__(256) grid_heads_kernel(const uint64_t* __restr
   }
 }
 
-// nearest point of the grid's frame among the cells that meet the cube [q - r, q + r]^3 (27 cells when the cell is the
-// radius r, at most 8 when it is 2 r: round 4 -- a look-up is a random probe of a hash table, and LiDAR cells are mostly
-// empty); returns index or -1, *d2out.  The candidates are a superset of the ball's points either way and ties go to the
-// lowest index, so the answer does not depend on the cell size.
-__device__ __forceinline__ void grid_scan_cell(const GridView& g, uint64_t key, int start, double qx, double qy, double qz,
-                                               double& best, int& arg) {
-  for (int64_t s = start; s < g.p; ++s) {
-    const GridRec r = g.rec[s];
-    if (r.key != key) break;
-    const int j = r.idx;
-    double ex = r.x - qx, ey = r.y - qy, ez = r.z - qz;
-    double d2 = __dadd_rn(__dadd_rn(__dmul_rn(ex, ex), __dmul_rn(ey, ey)), __dmul_rn(ez, ez));
-    if (d2 < best || (d2 == best && j < arg)) { best = d2; arg = j; }
-  }
-}
-
-__device__ __forceinline__ int grid_nearest(const GridView& g, const double* __restrict__ npts,
-                                            double qx, double qy, double qz, double r, double* d2out) {
-  const double rr = r * (1.0 + 1e-9) + 1e-12;            // (a point at exactly r must not fall off the cube through rounding)
-  const double fx0 = floor((qx - rr) / g.cell), fx1 = floor((qx + rr) / g.cell);
-  const double fy0 = floor((qy - rr) / g.cell), fy1 = floor((qy + rr) / g.cell);
-  const double fz0 = floor((qz - rr) / g.cell), fz1 = floor((qz + rr) / g.cell);
-  double best = INFINITY;
-  int arg = -1;
-  // a query that is NaN, +-Inf or whose cube leaves the key range matches nothing: told on the doubles, before any cast
-  // (a saturated bound would make the loops below endless)
-  if (!(cell_in_range(fx0) && cell_in_range(fx1) && cell_in_range(fy0) && cell_in_range(fy1) && cell_in_range(fz0) &&
-        cell_in_range(fz1))) {
-    *d2out = best;
-    return arg;
-  }
-  const int64_t x0 = (int64_t)fx0, x1 = (int64_t)fx1, y0 = (int64_t)fy0, y1 = (int64_t)fy1, z0 = (int64_t)fz0, z1 = (int64_t)fz1;
-  // (round 5, measured: probing the eight cells of a query in stages -- eight bitmap words, then the slots, then the values,
-  // each stage's loads in flight together -- 287.8 us against this loop's 289.1: the kernel is bound by the ~20 random
-  // 64-byte sectors a query touches beyond the L2s, 1.5 GB per launch, not by a thread's dependent chain)
-  for (int64_t ix = x0; ix <= x1; ++ix)
-    for (int64_t iy = y0; iy <= y1; ++iy)
-      for (int64_t iz = z0; iz <= z1; ++iz) {
-        uint64_t key = cell_key(ix, iy, iz);
-        if (g.t.bits != nullptr) {      // an empty cell is the common answer: told by the bitmap, from the L2s
-          const uint64_t b = bit_of(mix_key(key), g.t.mask);
-          if (!((g.t.bits[b >> 5] >> (b & 31)) & 1u)) continue;
-        }
-        int start = table_lookup(g.t, key);
-        if (start < 0) continue;
-        grid_scan_cell(g, key, start, qx, qy, qz, best, arg);
-      }
-  *d2out = best;
-  return arg;
-}
-
+// (the radius-limited nearest neighbour over a grid, grid_nearest, is grid.h's: icp.hip asks the same question)
 constexpr int MAXNEI = 32;
 struct NeiArgs {
   const void* grid[MAXNEI];
@@ -288,20 +221,7 @@ struct NeiArgs {
 };
 
 __device__ __forceinline__ GridView nei_grid(const NeiArgs& nei, int n, double cell) {
-  GridView g;
-  char* base = (char*)nei.grid[n] + 64;
-  g.t.keys = (unsigned long long*)base;
-  g.t.vals = (int*)(base + nei.cap[n] * 8);
-  g.t.mask = (uint64_t)nei.cap[n] - 1;
-  const int64_t q = nei.p[n] > 0 ? nei.p[n] : 1;
-  g.t.bits = (unsigned*)(base + grid_off_bits(nei.cap[n], q));
-  g.t.sbits = nullptr; g.t.hdr = nullptr;
-  g.keys = (const uint64_t*)(base + grid_off_skeys(nei.cap[n]));
-  g.idx = (const int*)(base + grid_off_sidx(nei.cap[n], q));
-  g.rec = (const GridRec*)(base + grid_off_spts(nei.cap[n], q));
-  g.p = nei.p[n];
-  g.cell = cell;
-  return g;
+  return grid_view(nei.grid[n], nei.p[n], nei.cap[n], cell);
 }
 
 // Stage 1: one thread per (neighbour frame, query point): the nearest point of that frame within
