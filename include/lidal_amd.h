@@ -651,6 +651,30 @@ int lidal_view_mean_softmax(const float* logits, const int64_t* inverse, int rep
 int lidal_view_scores(const float* logits, const int64_t* inverse, int reps, int64_t p, int c, float* prob,
                       int64_t* pred, double* viewd, float* viewe, int32_t* agree, void* stream);
 
+/* The same launch shape for MC-dropout: the `reps` rows of a point are the passes of ONE view under different dropout
+ * masks.  prob, pred: the same bytes as lidal_view_mean_softmax; p_v the same soft-max rows.
+ * With H(q) = sum_k (q_k > 0 ? -q_k log q_k : 0), an f64 expression of the f32 q_k summed in f64 in class order (no
+ * epsilon, no renormalisation), S = sum_v H(p_v) in view order (the rounding error of every add kept and added at the
+ * end) and m = the f32 nearest to the mean of the rows (their f64 sum in view order over reps; within one unit in the
+ * last place of prob, which stays the f32 chain of lidal_view_mean_softmax) -- so that agreeing passes score exactly 0:
+ *   bald f64 [p] = H(m) - S / reps      the mutual information between the prediction and the mask (BALD)
+ *   ment f32 [p] = (float)(S / reps)    the mean entropy of the passes
+ *   agree i32 [p] = as in lidal_view_scores. */
+int lidal_mc_scores(const float* logits, const int64_t* inverse, int reps, int64_t p, int c, float* prob,
+                    int64_t* pred, double* bald, float* ment, int32_t* agree, void* stream);
+
+/* ---- counter-based dropout ------------------------------------------------------------------ */
+/* In place on a contiguous tensor of n_elems F32 or BF16 elements: x[i] = rn_dtype((float)x[i] * m), m = scale where the
+ * element is kept, 0.0f where it is dropped (a dropped NaN stays NaN).  The mask is a pure function of (seed, call,
+ * element index): with e = first + i, Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9,
+ * 0xBB67AE85) under key (seed lo, seed hi) and counter (g lo, g hi, call lo, call hi), g = e >> 2, gives four words;
+ * element e is kept iff word e & 3 is below thr.  The host forms thr = min(floor((1 - p) * 2^32), 0xffffffff) and
+ * scale = (float)(1 / (1 - p)).  Nothing is stored for the backward pass: it is the same call on the gradient.
+ * One launch; refused before any launch when first % 8 != 0, thr is outside [0, 2^32), x is not 16-byte aligned,
+ * n_elems < 0 or the dtype is neither. */
+int lidal_dropout_apply(void* x, int64_t n_elems, int dtype, int64_t first, int64_t seed, int64_t call, int64_t thr,
+                        double scale, void* stream);
+
 /* replaces evaluate.py:100-109 + utils/iou_sk.py:14-19 ("next" row 8f-4): conf i32 [c*c] +=
  * bincount(argmax(logits[inverse]) * c + labels) over labelled points (label < 100); conf is
  * accumulated across calls (the caller zeroes it once and all-reduces it across ranks). */
@@ -1090,7 +1114,7 @@ enum {
   LIDAL_OP_FORK_SIDE = 26, LIDAL_OP_JOIN_SIDE = 27, LIDAL_OP_CONV_APPLY_IMAGE_WS = 28,
   LIDAL_OP_CONV_DGRAD_BN_SUMS_WS = 29, LIDAL_OP_ADD_RELU_BWD_BN_SUMS = 30, LIDAL_OP_BN_BWD_FROM_SUMS = 31,
   LIDAL_OP_ADD_RELU_BWD_BN_TILE_SUMS = 32, LIDAL_OP_DEVOXELIZE_BWD_CELLS = 33,
-  LIDAL_OP_CONV_WGRAD_STREAMS = 34
+  LIDAL_OP_CONV_WGRAD_STREAMS = 34, LIDAL_OP_DROPOUT_APPLY = 35
 };
 #define LIDAL_OP_FLAG_SIDE 1
 int lidal_plan_op_args(int kind);

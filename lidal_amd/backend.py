@@ -142,6 +142,8 @@ SIGNATURES = {
     'lidal_lovasz_bwd': (_i32, [_vp, _i32, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lidal_view_mean_softmax': (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     'lidal_view_scores': (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lidal_mc_scores': (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lidal_dropout_apply': (_i32, [_vp, _i64, _i32, _i64, _i64, _i64, _i64, _f64, _vp]),
     'lidal_confusion_accumulate': (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     'lidal_register_points': (_i32, [_vp, _i64, _vp, _vp, _vp]),
     'lidal_nn_grid_bytes': (_i64, [_i64]),

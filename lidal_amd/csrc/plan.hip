@@ -236,6 +236,7 @@ const OpInfo kOps[] = {
     /* LIDAL_OP_ADD_RELU_BWD_BN_TILE_SUMS 32 */ {15, "add_relu_bwd_bn_tile_sums"},
     /* LIDAL_OP_DEVOXELIZE_BWD_CELLS 33 */ {12, "devoxelize_bwd_cells"},
     /* LIDAL_OP_CONV_WGRAD_STREAMS 34 */ {15, "conv_wgrad_streams"},
+    /* LIDAL_OP_DROPOUT_APPLY 35 */ {8, "dropout_apply"},
 };
 constexpr int kNumOps = (int)(sizeof(kOps) / sizeof(kOps[0]));
 
@@ -502,6 +503,9 @@ int run_ops(const int64_t* words, int64_t n_words, int64_t n_ops, void* const* s
         break;
       case LIDAL_OP_VIEW_MEAN_SOFTMAX:
         rc = lidal_view_mean_softmax(CP(float, 0), CP(int64_t, 1), I(2), L(3), I(4), MP(float, 5), MP(int64_t, 6), st);
+        break;
+      case LIDAL_OP_DROPOUT_APPLY:
+        rc = lidal_dropout_apply(P(0), L(1), I(2), L(3), L(4), L(5), L(6), as_double(a[7]), st);
         break;
       case LIDAL_OP_FORK_SIDE: {         // side stream i (the flags; 0 means 1) waits for everything queued on the main stream so far
         const int i = sidx ? sidx : 1;

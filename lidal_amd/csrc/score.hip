@@ -121,6 +121,79 @@ __global__ void __launch_bounds__(256) view_scores_kernel(const float* __restric
   agree[i] = votes;
 }
 
+// ---------------- MC-dropout: mutual information of the passes ----------------
+// H(q) = sum_k (q_k > 0 ? -q_k log q_k : 0): an f64 expression of the f32 q_k, summed in f64 in class order
+__device__ __forceinline__ double entropy_f64(const float (&q)[kMaxClasses], int c) {
+  double h = 0.0;
+#pragma unroll
+  for (int k = 0; k < kMaxClasses; ++k)
+    if (k < c && q[k] > 0.f) h += -(double)q[k] * log((double)q[k]);
+  return h;
+}
+
+// view_scores_kernel's shape (the view mean first, then the rows a second time), with the `reps` rows of a point being
+// the passes of one view under different masks: bald = H(m) - (1 / reps) sum_v H(p_v), ment = that mean entropy.
+// prob, pred and agree as in view_scores_kernel.
+//
+// Two sums are taken more exactly than a chain of rounded adds, so that passes that agree score exactly 0 whatever their
+// number (five or more equal addends do not sum exactly in a chain):
+//  * the m of H(m) is the f32 nearest to the mean of the rows -- their f64 sum in pass order (exact for equal rows, and
+//    within 2^-53 of exact otherwise) over reps, rounded once.  prob stays view_mean_softmax_kernel's f32 chain, byte
+//    for byte; the two differ by at most a unit in the last place of an f32.
+//  * S = sum_v H(p_v) in pass order keeps the rounding error of every add (Knuth's two-sum) and adds their sum at the end.
+__global__ void __launch_bounds__(256) mc_scores_kernel(const float* __restrict__ logits,
+                                                        const int64_t* __restrict__ inverse, int reps, int64_t p, int c,
+                                                        float* __restrict__ prob, int64_t* __restrict__ pred,
+                                                        double* __restrict__ bald, float* __restrict__ ment,
+                                                        int* __restrict__ agree) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p) return;
+  float m[kMaxClasses];
+  double md[kMaxClasses];
+#pragma unroll
+  for (int j = 0; j < kMaxClasses; ++j) { m[j] = 0.f; md[j] = 0.0; }
+  for (int v = 0; v < reps; ++v) {
+    float x[kMaxClasses], mx, s;
+    row_exp<float>(logits + inverse[(int64_t)v * p + i] * c, c, x, mx, s);
+#pragma unroll
+    for (int j = 0; j < kMaxClasses; ++j)
+      if (j < c) {
+        const float q = x[j] / s;
+        m[j] = (v == 0) ? q : __fadd_rn(m[j], q);
+        md[j] = md[j] + (double)q;
+      }
+  }
+  float best = -INFINITY;
+  int arg = 0;
+  const float inv = (float)reps;
+#pragma unroll
+  for (int j = 0; j < kMaxClasses; ++j)
+    if (j < c) {
+      const float mean = m[j] / inv;
+      prob[i * c + j] = mean;
+      if (mean > best) { best = mean; arg = j; }
+      m[j] = (float)(md[j] / (double)reps);
+    }
+  pred[i] = arg;
+  double S = 0.0, S_err = 0.0;
+  int votes = 0;
+  for (int v = 0; v < reps; ++v) {
+    float x[kMaxClasses], mx, s;
+    votes += (row_exp<float>(logits + inverse[(int64_t)v * p + i] * c, c, x, mx, s) == arg) ? 1 : 0;
+#pragma unroll
+    for (int k = 0; k < kMaxClasses; ++k)
+      if (k < c) x[k] = x[k] / s;
+    const double h = entropy_f64(x, c);
+    const double t = S + h, hh = t - S;
+    S_err += (S - (t - hh)) + (h - hh);
+    S = t;
+  }
+  const double mean = (S + S_err) / (double)reps;
+  bald[i] = entropy_f64(m, c) - mean;
+  ment[i] = (float)mean;
+  agree[i] = votes;
+}
+
 // ---------------- confusion matrix of evaluate.py:100-109 + utils/iou_sk.py:14-19 ----------------
 // per point: voxel row through the inverse index, argmax over the c logits (first maximum, as
 // torch.max / np.argmax), and conf[pred * c + gt] += 1 for labelled points (gt < 100).  Integer
@@ -371,6 +444,17 @@ extern "C" int lidal_view_scores(const float* logits, const int64_t* inverse, in
   view_scores_kernel<<<(unsigned)cdiv(p, 256), 256, 0, (hipStream_t)stream>>>(
       logits, inverse, reps, p, c, prob, pred, viewd, viewe, agree);
   LIDAL_CHECK_LAUNCH("lidal_view_scores");
+  return 0;
+}
+
+extern "C" int lidal_mc_scores(const float* logits, const int64_t* inverse, int reps, int64_t p, int c, float* prob,
+                               int64_t* pred, double* bald, float* ment, int32_t* agree, void* stream) {
+  LIDAL_REQUIRE(c > 0 && c <= kMaxClasses, "mc_scores: classes must be in 1..%d", kMaxClasses);
+  LIDAL_REQUIRE(reps > 0, "mc_scores: reps must be positive");
+  if (p == 0) return 0;
+  mc_scores_kernel<<<(unsigned)cdiv(p, 256), 256, 0, (hipStream_t)stream>>>(
+      logits, inverse, reps, p, c, prob, pred, bald, ment, agree);
+  LIDAL_CHECK_LAUNCH("lidal_mc_scores");
   return 0;
 }
 

@@ -37,7 +37,7 @@ from . import backend as B
 __all__ = ['draw_augmentation', 'voxelize_scan', 'collate', 'parse_calibration', 'parse_poses',
            'register_scan', 'sk_label_map', 'nu_label_map', 'train_labels', 'train_sample', 'check_labels',
            'labeled_frames', 'frames_from_flag', 'kmeans_supervoxels', 'supervoxel_tables', 'balanced_assign',
-           'supervoxel_bounds', 'supervoxel_costs', 'voxelize_batch', 'score_sample', 'val_batch', 'train_batch',
+           'supervoxel_bounds', 'supervoxel_costs', 'voxelize_batch', 'score_sample', 'mc_sample', 'val_batch', 'train_batch',
            'score_frame_inputs', 'class_weights', 'Mix', 'identity_mix', 'wedge_vectors', 'class_mask', 'draw_lasermix',
            'draw_polarmix', 'mix_scans', 'mixed_train_batch']
 
@@ -345,6 +345,17 @@ def score_sample(points, intensity, inf_reps=8, rng=np.random):
     own draws (draw_augmentation(rng), in order), collated -- one voxelize_batch of views.  What infer_frame takes."""
     draws = [draw_augmentation(rng) for _ in range(int(inf_reps))]
     return voxelize_batch(points, intensity, [d[0] for d in draws], [d[1] for d in draws])
+
+
+def mc_sample(points, intensity, passes=8, rng=np.random, augment=False):
+    """The batch of an MC-dropout scoring pass (score/mc_dropout.py): ONE draw_augmentation(rng) repeated `passes`
+    times through voxelize_batch, so the collated copies of the scan are the same voxels and their rows differ by their
+    dropout masks alone (an element's mask depends on its index in the batch).  augment=True: score_sample -- every
+    pass its own view, the masks on top."""
+    if augment:
+        return score_sample(points, intensity, passes, rng)
+    trans_m, rnd = draw_augmentation(rng)
+    return voxelize_batch(points, intensity, [trans_m] * int(passes), [rnd] * int(passes))
 
 
 def _batch_scans(scans, others, what):

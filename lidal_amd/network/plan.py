@@ -22,9 +22,12 @@ Results are bitwise those of the per-operator path (tests/test_plan_gpu.py: loss
 gradient, every BatchNorm buffer, both networks, f32 and bf16), which stays in the package as the reference
 the plan is checked against (LIDAL_PLAN=0 selects it).
 
-What still goes through torch inside a planned step: the two in-place dropouts of SPVCNN (network/spvcnn.py:
-139,147: torch's generator decides the mask; the plan is cut in three around them), the flat gradient buffer and
-its per-parameter views (one call), and the optimizer.
+What still goes through torch inside a planned step: the two in-place dropouts of SPVCNN WHEN the model keeps
+nn.Dropout (network/spvcnn.py:139,147: torch's generator decides the mask; the plan is cut in three around them, and
+every cut joins the side streams), the flat gradient buffer and its per-parameter views (one call), and the optimizer.
+With the counter-based form (nn/dropout.py: SPVCNN(dropout_seed=...) or nn.use_counter_dropout) a dropout is one more
+operation of the plan -- OP_DROPOUT_APPLY, the same call on the gradient in the backward plan, nothing stored between
+them -- and a pass is ONE plan again; in eval mode under nn.mc_dropout the inference plan carries it too.
 """
 import array
 import ctypes
@@ -39,6 +42,7 @@ from ..nn.functional import norm as _N
 from ..nn.functional import devoxelize as _DV
 from ..nn.functional.invlist import inverse_lists
 from ..nn.functional.voxelize import _index32
+from ..nn.dropout import Dropout as _CounterDropout, mask_constants, _i64
 
 __all__ = ['planned_forward', 'enabled', 'COUNTERS']
 
@@ -53,7 +57,7 @@ OP_VOXELIZE_BWD, OP_DEVOXELIZE_FWD, OP_DEVOXELIZE_BWD_SORTED, OP_CE_FWD, OP_CE_B
 OP_COPY2D, OP_ADD2D, OP_TRANSPOSE_F32, OP_CAST_ROWS_BF16, OP_VIEW_MEAN_SOFTMAX = 21, 22, 23, 24, 25
 OP_FORK_SIDE, OP_JOIN_SIDE, OP_CONV_APPLY_IMAGE_WS, OP_CONV_DGRAD_BN_SUMS_WS = 26, 27, 28, 29
 OP_ADD_RELU_BWD_BN_SUMS, OP_BN_BWD_FROM_SUMS, OP_ADD_RELU_BWD_BN_TILE_SUMS, OP_DEVOXELIZE_BWD_CELLS = 30, 31, 32, 33
-OP_CONV_WGRAD_STREAMS = 34
+OP_CONV_WGRAD_STREAMS, OP_DROPOUT_APPLY = 34, 35
 
 # operations executed inside plans ('ops') and plans run ('plans') since import (backend.HITS counts every
 # library call made from Python, 'plan_run' among them)
@@ -108,7 +112,7 @@ _HIT_NAMES = {1: 'conv_weight_image', 2: 'conv_apply', 3: 'conv_apply', 4: 'conv
               16: 'voxelize_bwd', 17: 'devoxelize_fwd', 18: 'devoxelize_bwd_sorted', 19: 'ce_fwd', 20: 'ce_bwd',
               21: 'copy2d', 22: 'add2d', 23: 'transpose_f32', 24: 'cast_rows_bf16', 25: 'view_mean_softmax',
               26: 'fork_side', 27: 'join_side', 28: 'conv_apply', 29: 'conv_apply', 30: 'add_relu_bwd', 31: 'bn_bwd',
-              32: 'add_relu_bwd', 33: 'devoxelize_bwd_cells', 34: 'conv_wgrad_streams'}
+              32: 'add_relu_bwd', 33: 'devoxelize_bwd_cells', 34: 'conv_wgrad_streams', 35: 'dropout_apply'}
 
 
 def _tally(words):
@@ -326,11 +330,9 @@ class _Program:
         self.classifier = lin(model.classifier[0], False)
         self.n_class = self.classifier.co
         self.points = []
-        self.dropout = None
-        if self.spvcnn:
+        if self.spvcnn:         # (model.dropout is read when a step is written: it has no parameters and may be swapped)
             for seq in model.point_transforms:
                 self.points.append((lin(seq[0], True), bn(seq[1], True)))
-            self.dropout = model.dropout
         assert self.used == set(range(len(self.params))), 'a parameter of the model is not part of the plan'
         # where each parameter's gradient lives in the flat f32 buffer (whole 16-byte vectors; the odd-sized ones last,
         # and the classifier's bias ALWAYS the very last: its column sum is taken over the padded logits' columns and
@@ -890,7 +892,10 @@ class _Run:
     def f_dropout(self, addr, n, c):
         """nn.Dropout(p, inplace=True) on arena memory, with torch's own kernels and generator (ATen Dropout.cpp
         _dropout_impl, in-place form): noise = empty_like(x).bernoulli_(1 - p).div_(1 - p); x.mul_(noise)."""
-        d = self.prog.dropout
+        d = self.model.dropout
+        if isinstance(d, _CounterDropout):
+            self.noise.append(self.counter_dropout(d, addr, n * c))
+            return
         if d is None or not d.training or d.p == 0:
             self.noise.append(None)
             return
@@ -903,6 +908,20 @@ class _Run:
         noise = torch.empty_like(x).bernoulli_(1 - d.p).div_(1 - d.p)
         x.mul_(noise)
         self.noise.append(noise)
+
+    def counter_dropout(self, d, addr, numel, mask=None):
+        """The counter form (nn/dropout.py) as ONE operation of the plan, in place, no flush: `addr` was written by the
+        main stream's previous operation and nothing queued on an open side stream reads or writes it (DESIGN.md section
+        23).  mask None: a new application of module d -- draws its call id; -> the mask (thr, scale, seed, call) for the
+        backward pass to repeat on the gradient, or None when the module is not active."""
+        if mask is None:
+            if not d.active():
+                return None
+            mask = mask_constants(d.p) + (_i64(d.seed), _i64(d.draw()))
+        thr, scale, seed, call = mask
+        self.w += (OP_DROPOUT_APPLY, addr, numel, self.code, 0, seed, call, thr, _dbits(scale))
+        self.nops += 1
+        return mask
 
     def forward(self):
         prog, T, A = self.prog, self.T, self.arena
@@ -1181,6 +1200,9 @@ class _Run:
         noise = self.noise[which]
         if noise is None:
             return g
+        if isinstance(noise, tuple):
+            self.counter_dropout(None, g, n * c, noise)
+            return g
         self.flush()
         gt = self.barena.tensor(g, (n, c), self.dtype)
         if isinstance(noise, int):
@@ -1369,7 +1391,9 @@ class _EvalRun(_Run):
         return out
 
     def f_dropout(self, addr, n, c):
-        return
+        d = self.model.dropout          # (nn.Dropout is the identity here; the counter form is active under nn.mc_dropout)
+        if isinstance(d, _CounterDropout):
+            self.counter_dropout(d, addr, n * c)
 
     def forward(self):
         out = _Run.forward(self)

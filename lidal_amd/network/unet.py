@@ -86,7 +86,9 @@ class MinkUNet(_SparseUNet):
 
 
 class SPVCNN(_SparseUNet):
-    def __init__(self, class_num):
+    def __init__(self, class_num, dropout_seed=None):
+        """dropout_seed: None keeps the reference's nn.Dropout (torch's generator decides the masks); an int builds the
+        counter-based form (nn/dropout.py: masks from (seed, call, element index), one launch plan per pass)."""
         super().__init__(class_num)
         cs = self.cs
         self.pres = 0.05
@@ -98,7 +100,7 @@ class SPVCNN(_SparseUNet):
             seq[0].bn_follows = True        # the Linear kernel leaves the BatchNorm's batch statistics
             seq[1].fused_relu = True
         self.weight_initialization()
-        self.dropout = nn.Dropout(0.3, True)
+        self.dropout = nn.Dropout(0.3, True) if dropout_seed is None else spnn.Dropout(0.3, True, dropout_seed)
 
     # strides at which features cross between the point and the voxel branch (forward below)
     POINT_STRIDES = (1, 16, 4)

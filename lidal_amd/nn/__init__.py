@@ -12,8 +12,10 @@ from ..tensor import SparseTensor
 from ..utils import make_ntuple
 from . import functional, utils
 from .functional import conv3d
+from .dropout import Dropout, mc_dropout, use_counter_dropout
 
-__all__ = ['Conv3d', 'BatchNorm', 'BatchNorm1d', 'Linear', 'ReLU', 'functional', 'utils', 'Deferred']
+__all__ = ['Conv3d', 'BatchNorm', 'BatchNorm1d', 'Linear', 'ReLU', 'functional', 'utils', 'Deferred',
+           'Dropout', 'use_counter_dropout', 'mc_dropout']
 
 # LIDAL_SURFACE_FUSION=0: every surface module computes its output when it is called (rounds 1-4)
 import os as _os

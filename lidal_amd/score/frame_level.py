@@ -10,6 +10,8 @@
   select_frames       the 1 % top-k of ENT / MAR / CONF / SEGENT (see reference_zero_half below)
   random_frames       frame_level/RAND.py's draw
   VIEWD / VIEWE / VOTE  beyond the reference: how much the augmented views of a frame disagreed (view_level.py)
+  BALD / MCENT          MC-dropout: the frame means of the mutual information and of the passes' mean entropy
+                        (mc_dropout.py); VOTE beside them is the variation ratio of the passes
   frame_sequence      infer_frame per frame, then only the requested scores (scalars, or a [96] vector for CSET)
   FrameBoard          all sequences' frames in train_split order (the reference's seq_offsets), the per-sequence flags
 
@@ -26,10 +28,11 @@ from .. import io
 __all__ = ['frame_uncertainty', 'segment_entropy', 'frame_feature', 'coreset', 'num_to_add', 'select_frames',
            'random_frames', 'frame_sequence', 'FrameBoard', 'METRICS', 'SK_TRAIN_SPLIT']
 
-METRICS = ('ENT', 'MAR', 'CONF', 'SEGENT', 'CSET', 'VIEWD', 'VIEWE', 'VOTE')
+METRICS = ('ENT', 'MAR', 'CONF', 'SEGENT', 'CSET', 'VIEWD', 'VIEWE', 'VOTE', 'BALD', 'MCENT')
 LARGEST = {'ENT': True, 'MAR': True, 'CONF': False, 'SEGENT': True,       # MAR: "largest", as the reference (sic)
-           'VIEWD': True, 'VIEWE': True, 'VOTE': True}
+           'VIEWD': True, 'VIEWE': True, 'VOTE': True, 'BALD': True, 'MCENT': True}
 VIEW_METRICS = ('VIEWD', 'VIEWE', 'VOTE')
+MC_METRICS = ('BALD', 'MCENT')
 SK_TRAIN_SPLIT = ['00', '01', '02', '03', '04', '05', '06', '07', '09', '10']
 MAX_CLASSES = 32
 MAX_FEAT_DIM = 128
@@ -201,7 +204,13 @@ def frame_sequence(model, frames, metrics=('ENT', 'MAR', 'CONF'), inf_reps=8, au
     feature only when CSET is asked), then only the requested values.  Frame dicts are score_sequence's (coords, feats,
     inverse; sv_ptr / sv_idx for SEGENT).  class_num (SEGENT) defaults to the model's class count.  Returns
     {metric: [per frame: f32 0-d (ENT / MAR / CONF / VIEWD / VIEWE / VOTE), f64 0-d (SEGENT) or f32 [D] (CSET) device
-    tensor]}.  VIEWD / VIEWE / VOTE come out of the same inference (view_level.frame_view_scores)."""
+    tensor]}.  VIEWD / VIEWE / VOTE come out of the same inference (view_level.frame_view_scores).  BALD / MCENT (f32
+    0-d) put the model under nn.mc_dropout for the whole pass (ValueError for a model without counter dropout): the
+    `inf_reps` rows of a point are then MC-dropout passes, every other metric asked for in the same call is taken of those
+    passes too, and VOTE is their variation ratio (mc_dropout.frame_mc_scores)."""
+    import contextlib
+    from ..nn import mc_dropout
+    from .mc_dropout import frame_mc_scores
     from .prob_inference import infer_frame
     from .view_level import frame_view_scores
     metrics = tuple(metrics)
@@ -209,26 +218,32 @@ def frame_sequence(model, frames, metrics=('ENT', 'MAR', 'CONF'), inf_reps=8, au
     if bad:
         raise ValueError('frame_sequence: unknown metrics %s (known: %s)' % (bad, METRICS))
     want_feat = 'CSET' in metrics
-    want_views = any(m in metrics for m in VIEW_METRICS)
+    want_mc = any(m in metrics for m in MC_METRICS)
+    want_views = any(m in metrics for m in (VIEW_METRICS[:2] if want_mc else VIEW_METRICS))
     out = {m: [] for m in metrics}
-    for d in frames:
-        r = infer_frame(model, d['coords'], d['feats'], d['inverse'], inf_reps, autocast=autocast,
-                        return_feat=want_feat, return_view_scores=want_views)
-        prob, pred = r[0], r[1]
-        if any(m in metrics for m in ('ENT', 'MAR', 'CONF')):
-            ent, mar, conf = frame_uncertainty(prob)
-            for m, v in (('ENT', ent), ('MAR', mar), ('CONF', conf)):
-                if m in out:
-                    out[m].append(v)
-        if 'SEGENT' in out:
-            out['SEGENT'].append(segment_entropy(pred, d['sv_ptr'], d['sv_idx'],
-                                                 prob.shape[1] if class_num is None else class_num))
-        if want_feat:
-            out['CSET'].append(frame_feature(r[2]))
-        if want_views:
-            for m, v in zip(VIEW_METRICS, frame_view_scores(*r[-1], inf_reps)):
-                if m in out:
-                    out[m].append(v)
+    with (mc_dropout(model) if want_mc else contextlib.nullcontext()):
+        for d in frames:
+            r = infer_frame(model, d['coords'], d['feats'], d['inverse'], inf_reps, autocast=autocast,
+                            return_feat=want_feat, return_view_scores=want_views, return_mc_scores=want_mc)
+            prob, pred = r[0], r[1]
+            if any(m in metrics for m in ('ENT', 'MAR', 'CONF')):
+                ent, mar, conf = frame_uncertainty(prob)
+                for m, v in (('ENT', ent), ('MAR', mar), ('CONF', conf)):
+                    if m in out:
+                        out[m].append(v)
+            if 'SEGENT' in out:
+                out['SEGENT'].append(segment_entropy(pred, d['sv_ptr'], d['sv_idx'],
+                                                     prob.shape[1] if class_num is None else class_num))
+            if want_feat:
+                out['CSET'].append(frame_feature(r[2]))
+            if want_views:
+                for m, v in zip(VIEW_METRICS, frame_view_scores(*r[-2 if want_mc else -1], inf_reps)):
+                    if m in out:
+                        out[m].append(v)
+            if want_mc:             # (VOTE: the same agree either way; taken here unless the view scores ran as well)
+                for m, v in zip(MC_METRICS + ('VOTE',), frame_mc_scores(*r[-1], inf_reps)):
+                    if m in out and not (m == 'VOTE' and want_views):
+                        out[m].append(v)
     return out
 
 

@@ -53,11 +53,12 @@ class _Inference:
     """infer_frame over this rank's frames in a fixed order, the coordinate tables of the NEXT frame built on a
     second stream beside the forward pass of the current one (network/geometry.py): a frame's forward then never
     waits for the host to learn the sizes of its own maps.  Returns the frame's prob; with view_scores its
-    (viewd, viewe, agree) instead (score/view_level.py)."""
+    (viewd, viewe, agree) instead (score/view_level.py), with mc_scores its (bald, ment, agree) (score/mc_dropout.py)."""
 
-    def __init__(self, model, by_id, order, inf_reps, autocast, prefetch, view_scores=False):
+    def __init__(self, model, by_id, order, inf_reps, autocast, prefetch, view_scores=False, mc_scores=False):
         self.model, self.by_id, self.order = model, by_id, list(order)
         self.inf_reps, self.autocast, self.view_scores = inf_reps, autocast, view_scores
+        self.mc_scores = mc_scores
         self.pos = 0
         self.pf = self.g = None
         net = _backbone(model)
@@ -72,7 +73,8 @@ class _Inference:
         assert f == self.order[self.pos], 'frames are inferred in the announced order'
         d = self.by_id[f]
         out = infer_frame(self.model, d['coords'], d['feats'], d['inverse'], self.inf_reps,
-                          autocast=self.autocast, geometry=self.g, return_view_scores=self.view_scores)
+                          autocast=self.autocast, geometry=self.g, return_view_scores=self.view_scores,
+                          return_mc_scores=self.mc_scores)
         self.pos += 1
         if self.pf is not None:
             if self.pos < len(self.order):
@@ -80,6 +82,8 @@ class _Inference:
             else:                       # the last frame: fence the tables still held and hand them to the device state
                 self.g = None
                 self.pf.close()
+        if self.mc_scores:
+            return out[-1]
         return out[2] if self.view_scores else out[0]
 
 
