@@ -849,6 +849,37 @@ int lidal_radius_pairs_count(const float* centers, int64_t n, float radius, int6
 int lidal_radius_pairs_fill(const float* centers, int64_t n, float radius, const int64_t* row_ptr, int32_t* col,
                             void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- Euclidean clustering: instance ids of a labelled or predicted batch (csrc/cluster.hip) ---- */
+/* The connected components of the fixed-radius graph over the points of one class of one scan.  xyz f32 [p,3]: n_scans
+ * (1..32) scans laid end to end, point_ptr i64 [n_scans + 1] on the HOST (ascending from 0 to p); labels i64 [p] or
+ * NULL (every point has class 0); tol f32 [64] on the HOST: class c is clustered iff tol[c] > 0, and such a tolerance
+ * lies in [2^-10, 2^10] m.  A point is live iff its coordinates are finite, 0 <= label < 64 and tol[label] > 0.  Two
+ * live points of one scan and one class c are joined iff
+ *     sqrt(((dx*dx + dy*dy) + dz*dz)) < tol[c]        in f32, every operation rounded, the root correctly rounded;
+ * a component is kept iff min_points <= size <= max_points (1 <= min_points <= max_points).  Outputs, all on the device
+ * and all a function of the input alone:
+ *   inst i32 [p]             the instance id of a point, -1 when it is not live or its component is not kept; the K kept
+ *                            components are numbered in ascending order of their smallest row
+ *   cls i32 [K], bbox f32 [K,6]      class; min x, y, z, max x, y, z over the members          (allocate for K = p)
+ *   member_ptr i64 [K + 1], members i32 [p]    instance k owns members[member_ptr[k] .. member_ptr[k + 1]), ascending
+ *                            rows; the rows past member_ptr[K] are scratch
+ *   status i64 [2 n_scans + 3]       word 0: 0 or a LIDAL_CLUSTERS_ word; then inst_ptr [n_scans + 1]: scan s owns the
+ *                            ids inst_ptr[s] .. inst_ptr[s + 1], K = inst_ptr[n_scans]; then member_start [n_scans + 1] =
+ *                            member_ptr[inst_ptr[s]], where the members of the scan's instances begin
+ * A live point whose cell index (cell = the smallest power of two >= the largest tolerance) does not fit 21 bits raises
+ * CELL_RANGE and is treated as not live; WALK says a union-find walk ran out of its step bound (a defect, never an
+ * input).  p < 2^30.  With p = 0 or no positive tolerance there is no instance: the call returns 0, launches nothing and
+ * writes nothing (every inst is then -1 by definition).  Refusals come before the first launch. */
+enum {
+  LIDAL_CLUSTERS_CELL_RANGE = 1,  /* a live point outside the 21 bits per axis of the cell key */
+  LIDAL_CLUSTERS_WALK = 2         /* a walk or a retry loop of the union-find ran out of its bound */
+};
+int64_t lidal_euclidean_clusters_workspace_bytes(int64_t p, int n_scans);
+int lidal_euclidean_clusters(const float* xyz, const int64_t* labels, int64_t p, const int64_t* point_ptr_host,
+                             int n_scans, const float* tol_host, int64_t min_points, int64_t max_points, int32_t* inst,
+                             int32_t* cls, int64_t* member_ptr, int32_t* members, float* bbox, int64_t* status, void* ws,
+                             int64_t ws_bytes, void* stream);
+
 /* ---- ReDAL region selection (score/sv_level/ReDAL.py, dataset/ReDAL/gen_surface_variation_sk.py; csrc/redal.hip) ---- */
 /* k nearest OTHER points of every point of a raw scan xyz f32 [p,3]: knn i32 [p,k], sorted by (f64 distance, index).
  * 1 <= k <= 64; p < k + 1 is refused (status 2, lidal_last_error).  `cell`: the search grid's cell in metres (the

@@ -26,6 +26,11 @@ Mixed batches (the project's own definition, nothing of th
 mixed samples -- inclination bands or an azimuth sector of two scans interleaved, rotated copies of the rows of chosen
 classes pasted -- in lidal_mix_scans with one read-back; `draw_lasermix` / `draw_polarmix` make the `Mix` records on the
 host and `mixed_train_batch` puts the step in front of voxelize_batch.
+
+Instances (the project's own definition): `euclidean_clusters` turns labels or predictions into
+instance ids -- the connected components of the fixed-radius graph per scan and class -- in lidal_euclidean_clusters
+with one read-back; `Instances.as_csr` hands a scan's instances to `train_labels` as regions, `draw_instance_paste`
+picks instances for a paste and `mix_scans(paste_masks=...)` pastes those rows only.
 """
 import math
 
@@ -39,7 +44,7 @@ __all__ = ['draw_augmentation', 'voxelize_scan', 'collate', 'parse_calibration',
            'labeled_frames', 'frames_from_flag', 'kmeans_supervoxels', 'supervoxel_tables', 'balanced_assign',
            'supervoxel_bounds', 'supervoxel_costs', 'voxelize_batch', 'score_sample', 'mc_sample', 'val_batch', 'train_batch',
            'score_frame_inputs', 'class_weights', 'Mix', 'identity_mix', 'wedge_vectors', 'class_mask', 'draw_lasermix',
-           'draw_polarmix', 'mix_scans', 'mixed_train_batch']
+           'draw_polarmix', 'mix_scans', 'mixed_train_batch', 'Instances', 'euclidean_clusters', 'draw_instance_paste']
 
 SCALE = 20                # sk_dataset.py:56
 FULL_SCALE = 8192
@@ -587,7 +592,24 @@ def _mix_arguments(n_points, mixes, has_labels):
     return desc, slots, ptr
 
 
-def mix_scans(points, intensity, labels, mixes):
+def _paste_key(labs, paste_masks, what):
+    """The labels the mix is steered with: the label where a scan's mask is set, 255 (never pasted) elsewhere."""
+    masks = list(paste_masks)
+    if len(masks) != len(labs):
+        raise ValueError('%s: %d paste masks for %d scans' % (what, len(masks), len(labs)))
+    keys = []
+    for j, (l, m) in enumerate(zip(labs, masks)):
+        if m is None:
+            keys.append(l)
+            continue
+        if not torch.is_tensor(m) or m.dtype != torch.bool or m.numel() != l.numel():
+            raise ValueError('%s: scan %d: the paste mask must be a bool tensor over its %d rows' % (what, j, l.numel()))
+        B.require_gpu(m)
+        keys.append(torch.where(m.reshape(-1), l, torch.full_like(l, 255)))
+    return keys
+
+
+def mix_scans(points, intensity, labels, mixes, paste_masks=None):
     """M = len(mixes) mixed samples from S scans in ONE library call (lidal_mix_scans: three launches, no atomics) with
     one read-back.
       points / intensity   lists of S GPU tensors f32 [P_s,3] / [P_s], as voxelize_batch takes them
@@ -601,7 +623,11 @@ def mix_scans(points, intensity, labels, mixes):
     allocated at the slot bound sum(n_a + n_b (1 + rotations)) and returned as slices.  ValueError, before anything
     touches the device, for no mixes or more than 32, a scan index out of range, more than 31 boundaries or boundaries
     that are not finite and ascending, a sector that is not finite, mask bits at or above the cell count, more than 4
-    rotations, a paste without labels and 2^30 or more slots."""
+    rotations, a paste without labels and 2^30 or more slots.
+
+    paste_masks (a list with one bool tensor [P_s] on the device, or None, per scan) restricts the pastes to the rows
+    whose mask is set -- the rows of chosen instances (draw_instance_paste): the call is steered with the label where
+    the mask is set and 255 elsewhere, and the labels returned are labels[src].  A scan with None pastes as before."""
     what = 'mix_scans'
     pts, inten = list(points), list(intensity)
     labs = None if labels is None else list(labels)
@@ -615,6 +641,8 @@ def mix_scans(points, intensity, labels, mixes):
             if other is not None and (not torch.is_tensor(other[j]) or other[j].numel() != x.shape[0]):
                 raise ValueError('%s: scan %d: %d %s for %d points'
                                  % (what, j, other[j].numel() if torch.is_tensor(other[j]) else -1, name, x.shape[0]))
+    if paste_masks is not None and labs is None:
+        raise ValueError('%s: paste masks need labels' % what)
     desc, slots, _ = _mix_arguments([x.shape[0] for x in pts], mixes, labs is not None)
     m = len(desc)
     B.require_gpu(*pts, *inten, *(labs or []))
@@ -626,6 +654,10 @@ def mix_scans(points, intensity, labels, mixes):
     if labs is not None:
         labs = [l.to(torch.int64).contiguous().reshape(-1) for l in labs]
         lab_all = labs[0] if len(labs) == 1 else torch.cat(labs)
+    key_all = lab_all
+    if paste_masks is not None:
+        keys = _paste_key(labs, paste_masks, what)
+        key_all = keys[0] if len(keys) == 1 else torch.cat(keys)
     dev = xyz.device
     cap = max(slots, 1)
     out_xyz = B.empty((cap, 3), torch.float32, dev)
@@ -635,18 +667,20 @@ def mix_scans(points, intensity, labels, mixes):
     counts = torch.empty(m + 1 + 6 * m, dtype=torch.int64, device=dev)               # point_ptr [M+1] | parts [M,6]
     ws_bytes = B.lib().lidal_mix_scans_workspace_bytes(slots, m)
     ws = B.workspace(ws_bytes, dev)
-    B.check(B.lib().lidal_mix_scans(B.ptr(xyz), B.ptr(w_all), B.ptr(lab_all), xyz.shape[0], desc.ctypes.data, m,
+    B.check(B.lib().lidal_mix_scans(B.ptr(xyz), B.ptr(w_all), B.ptr(key_all), xyz.shape[0], desc.ctypes.data, m,
                                     B.ptr(out_xyz), B.ptr(out_w), B.ptr(out_lab), B.ptr(out_src), B.ptr(counts),
                                     B.ptr(ws), ws_bytes, B.stream()), 'mix_scans')
     host = counts.cpu().numpy()                                                       # the one read-back
     point_ptr, parts = host[:m + 1].copy(), host[m + 1:].reshape(m, 6).copy()
     n = int(point_ptr[-1])
+    if paste_masks is not None:
+        out_lab = lab_all[out_src[:n]]                                                # the labels behind the steering key
     return {'points': out_xyz[:n], 'intensity': out_w[:n], 'labels': out_lab[:n] if out_lab is not None else None,
             'src': out_src[:n], 'point_ptr': point_ptr, 'parts': parts}
 
 
 def mixed_train_batch(scans, raw_labels, label_map, mixes, sv_csrs=None, sv_flags=None, pseudos=None, rng=np.random,
-                      check=True, extra_labels=None):
+                      check=True, extra_labels=None, paste_masks=None):
     """train_batch over mixed samples: scans, raw_labels, sv_csrs, sv_flags and pseudos as train_batch takes them, and
     one Mix per sample of the batch.  train_labels per scan (no read-back), mix_scans of the scans and their labels_p,
     ONE draw_augmentation(rng) per mix in order, voxelize_batch over the mixed samples, labels_v_b = the mixed
@@ -654,7 +688,8 @@ def mixed_train_batch(scans, raw_labels, label_map, mixes, sv_csrs=None, sv_flag
     train_step.  Beside it: labels_p_b and src_p_b per mixed point, src_b per voxel (rows of the concatenated input list:
     any per-point array of the scans follows the batch with array[src]) and parts of mix_scans.  Two read-backs: the
     mix's row counts and the batch's voxel counts.  identity_mix(j) for every scan gives train_batch's batch.
-    extra_labels as train_batch takes them: they fill the scans' labels_p before the scans are mixed."""
+    extra_labels as train_batch takes them: they fill the scans' labels_p before the scans are mixed.  paste_masks as
+    mix_scans takes them."""
     if (sv_csrs is None) != (sv_flags is None):
         raise ValueError('mixed_train_batch: sv_csrs and sv_flags come together')
     scans = _batch_scans(scans, [('label arrays', raw_labels), ('supervoxel lists', sv_csrs), ('flag arrays', sv_flags),
@@ -666,7 +701,7 @@ def mixed_train_batch(scans, raw_labels, label_map, mixes, sv_csrs=None, sv_flag
                         sv_flags[j] if sv_flags is not None else None, pseudos[j] if pseudos is not None else None,
                         check=False) for j in range(len(scans))]
     mixed = mix_scans([x for x, _ in scans], [w for _, w in scans],
-                      _fill_extra([o[0] for o in out], extra_labels, 'mixed_train_batch'), mixes)
+                      _fill_extra([o[0] for o in out], extra_labels, 'mixed_train_batch'), mixes, paste_masks=paste_masks)
     draws = [draw_augmentation(rng) for _ in mixes]
     ptr = mixed['point_ptr']
     cut = [(int(ptr[j]), int(ptr[j + 1])) for j in range(len(mixes))]
@@ -1050,6 +1085,138 @@ def vccs_supervoxels(points, voxel_resolution=0.5, seed_resolution=10.0, spatial
                           owners=owners[v0:v1].long(), counts=counts[s0:s1], rounds=rounds, min_seed=min_seed),)
         out.append(item)
     return out[0] if single else out
+
+
+MAX_CLUSTER_SCANS = 32
+MAX_CLUSTER_POINTS = 2 ** 30 - 1
+N_CLUSTER_CLASSES = 64
+_CLUSTER_ERRORS = {1: 'a live point lies outside the 21 bits per axis of the cell key',
+                   2: 'a union-find walk ran out of its step bound'}
+
+
+class Instances:
+    """The instances of one euclidean_clusters call.  On the device: inst i32 [P] (-1: no instance), cls i32 [K],
+    member_ptr i64 [K+1], members i32 (point rows of the batch, ascending within an instance), bbox f32 [K,6] (min x,
+    y, z, max x, y, z) and sizes i64 [K].  On the host: inst_ptr i64 [S+1] (scan s owns the ids inst_ptr[s] ..
+    inst_ptr[s+1]), point_ptr i64 [S+1] of the input and member_start i64 [S+1] = member_ptr[inst_ptr]."""
+    __slots__ = ('inst', 'inst_ptr', 'cls', 'member_ptr', 'members', 'bbox', 'sizes', 'point_ptr', 'member_start')
+
+    def __init__(self, **kw):
+        for k in Instances.__slots__:
+            setattr(self, k, kw[k])
+
+    def __len__(self):
+        return int(self.inst_ptr[-1])
+
+    def as_csr(self, scan):
+        """(ptr i64 [n+1], members i64) of scan `scan`'s n instances with scan-local rows: the sv_csr of train_labels."""
+        k0, k1 = int(self.inst_ptr[scan]), int(self.inst_ptr[scan + 1])
+        m0, m1 = int(self.member_start[scan]), int(self.member_start[scan + 1])
+        return self.member_ptr[k0:k1 + 1] - m0, self.members[m0:m1].long() - int(self.point_ptr[scan])
+
+
+def _tolerance_table(tolerance, what):
+    tol = np.zeros(N_CLUSTER_CLASSES, dtype=np.float32)
+    items = tolerance.items() if isinstance(tolerance, dict) else [(c, tolerance) for c in range(N_CLUSTER_CLASSES)]
+    for c, t in items:
+        if not 0 <= int(c) < N_CLUSTER_CLASSES or int(c) != c:
+            raise ValueError('%s: class id %r is outside 0..63' % (what, c))
+        t32 = np.float32(t)
+        if not (t32 >= 0):
+            raise ValueError('%s: the tolerance %r of class %d is negative or NaN' % (what, t, c))
+        if t32 > 0 and not 2.0 ** -10 <= t32 <= 2.0 ** 10:
+            raise ValueError('%s: the tolerance %r of class %d is outside [2^-10, 2^10] m' % (what, t, c))
+        tol[int(c)] = t32
+    return tol
+
+
+def euclidean_clusters(points, labels=None, tolerance=0.5, min_points=1, max_points=None):
+    """Instance ids by Euclidean clustering on the GPU (what PCL calls EuclideanClusterExtraction,
+    in this project's own definition -- PCL's cluster order is not reproduced, the partition is the same): the connected
+    components of the graph that joins two points of one scan and one class c whose f32 distance is below tolerance[c].
+
+      points      f32 [P,3] on the GPU, or a list of 1..32 such scans (one call), as vccs_supervoxels takes them
+      labels      i64 [P] (or a list): the labels_p of train_labels, or predictions; None: every point has class 0.
+                  A point with a label outside 0..63, a class without a tolerance or a coordinate that is not finite has
+                  no instance and joins nothing.
+      tolerance   metres, one float for every class or {class: metres}; 0 = the class is not clustered
+      min_points, max_points   the sizes kept (max_points=None: any)
+    Returns an Instances record; the ids run scan after scan, in ascending order of an instance's smallest row.  One
+    read-back (the instance counts).  ValueError, before the device is touched, for what the definition refuses, and
+    after the call for a live point too far out for the cell key."""
+    what = 'euclidean_clusters'
+    tol = _tolerance_table(tolerance, what)
+    if int(min_points) != min_points or min_points < 1:
+        raise ValueError('%s: min_points=%r must be an integer >= 1' % (what, min_points))
+    if max_points is not None and (int(max_points) != max_points or max_points < min_points):
+        raise ValueError('%s: max_points=%r is below min_points=%r' % (what, max_points, min_points))
+
+    def check(frames):
+        if len(frames) > MAX_CLUSTER_SCANS:
+            raise ValueError('%s: %d scans in one call (at most %d)' % (what, len(frames), MAX_CLUSTER_SCANS))
+        if sum(x.shape[0] for x in frames) > MAX_CLUSTER_POINTS:
+            raise ValueError('%s: %d points in one batch (fewer than 2^30)' % (what, sum(x.shape[0] for x in frames)))
+        if labels is not None:
+            labs = [labels] if torch.is_tensor(labels) else list(labels)
+            if len(labs) != len(frames) or any(not torch.is_tensor(l) or l.numel() != x.shape[0]
+                                               for l, x in zip(labs, frames)):
+                raise ValueError('%s: the labels must match the points, scan by scan' % what)
+
+    frames, xyz, ptr, _ = _scan_batch(points, what, check)
+    n, dev, p = len(frames), xyz.device, int(ptr[-1])
+    lab_all = None
+    if labels is not None:
+        labs = [labels] if torch.is_tensor(labels) else list(labels)
+        B.require_gpu(*labs)
+        labs = [l.to(torch.int64).contiguous().reshape(-1) for l in labs]
+        lab_all = labs[0] if len(labs) == 1 else torch.cat(labs)
+    max_points = max(p, int(min_points)) if max_points is None else int(max_points)
+    i32 = dict(dtype=torch.int32, device=dev)
+    inst = torch.full((p,), -1, **i32)
+    if p == 0 or not (tol > 0).any():                                          # no instance: nothing to launch
+        zero = np.zeros(n + 1, dtype=np.int64)
+        return Instances(inst=inst, inst_ptr=zero, cls=torch.empty(0, **i32),
+                         member_ptr=torch.zeros(1, dtype=torch.int64, device=dev), members=torch.empty(0, **i32),
+                         bbox=torch.empty((0, 6), dtype=torch.float32, device=dev),
+                         sizes=torch.empty(0, dtype=torch.int64, device=dev), point_ptr=ptr, member_start=zero.copy())
+    cls, members = B.empty(p, torch.int32, dev), B.empty(p, torch.int32, dev)
+    member_ptr = B.empty(p + 1, torch.int64, dev)
+    bbox = B.empty((p, 6), torch.float32, dev)
+    status = torch.empty(1 + 2 * (n + 1), dtype=torch.int64, device=dev)
+    nbytes = B.lib().lidal_euclidean_clusters_workspace_bytes(p, n)
+    ws = B.workspace(nbytes, dev)
+    B.check(B.lib().lidal_euclidean_clusters(B.ptr(xyz), B.ptr(lab_all), p, ptr.ctypes.data, n, tol.ctypes.data,
+                                             int(min_points), max_points, B.ptr(inst), B.ptr(cls), B.ptr(member_ptr),
+                                             B.ptr(members), B.ptr(bbox), B.ptr(status), B.ptr(ws), nbytes, B.stream()),
+            'euclidean_clusters')
+    host = status.cpu().numpy()                                                # the one read-back
+    if host[0] == 1:
+        raise ValueError('%s: %s' % (what, _CLUSTER_ERRORS[1]))
+    if host[0] != 0:
+        raise RuntimeError('%s: %s (error word %d)' % (what, _CLUSTER_ERRORS.get(int(host[0]), '?'), int(host[0])))
+    inst_ptr, member_start = host[1:n + 2].copy(), host[n + 2:2 * n + 3].copy()
+    k, m = int(inst_ptr[-1]), int(member_start[-1])
+    member_ptr = member_ptr[:k + 1]
+    return Instances(inst=inst, inst_ptr=inst_ptr, cls=cls[:k], member_ptr=member_ptr, members=members[:m], bbox=bbox[:k],
+                     sizes=member_ptr[1:] - member_ptr[:-1], point_ptr=ptr, member_start=member_start)
+
+
+def draw_instance_paste(instances, scan, rng=np.random, classes=(), n_inst=1):
+    """A paste mask for mix_scans(paste_masks=...): bool [P_scan] on the device, set on the rows of the chosen instances
+    of scan `scan`.  The candidates are the scan's instances whose class is in `classes`, in id order; ONE
+    rng.choice(len(candidates), size=min(n_inst, len(candidates)), replace=False) picks among them.  Without candidates
+    (or with n_inst = 0) nothing is drawn and the mask is empty.  The classes are read back (one small copy)."""
+    k0, k1 = int(instances.inst_ptr[scan]), int(instances.inst_ptr[scan + 1])
+    a, b = int(instances.point_ptr[scan]), int(instances.point_ptr[scan + 1])
+    wanted = sorted(set(int(c) for c in classes))
+    cls = instances.cls[k0:k1].cpu().numpy() if k1 > k0 else np.zeros(0, dtype=np.int32)
+    cand = k0 + np.nonzero(np.isin(cls, wanted))[0]
+    local = instances.inst[a:b]
+    take = min(int(n_inst), len(cand))
+    if take <= 0:
+        return torch.zeros(b - a, dtype=torch.bool, device=local.device)
+    chosen = cand[np.asarray(rng.choice(len(cand), size=take, replace=False)).reshape(-1)]
+    return torch.isin(local, torch.from_numpy(chosen.astype(np.int32)).to(local.device))
 
 
 def supervoxel_tables(labels_per_frame, frame_names, ignore_label=None, min_points=0):
