@@ -35,7 +35,7 @@ def _stale(target, deps):
 
 def _compile(src):
     obj = os.path.join(OBJ, src + '.o')
-    deps = [os.path.join(CSRC, src), os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'grid.h'),
+    deps = [os.path.join(CSRC, src), os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'grid.h'), os.path.join(CSRC, 'cellsort.h'),
             os.path.join(CSRC, 'npsum.h'), os.path.join(CSRC, 'kmeans.h'), os.path.join(CSRC, 'sym3.h'), os.path.join(CSRC, 'scan.h'),
             os.path.join(CSRC, 'multi_tensor.h'), os.path.join(CSRC, 'rows.h'),
             os.path.join(HERE, '..', 'include', 'lidal_amd.h'), os.path.abspath(__file__)]

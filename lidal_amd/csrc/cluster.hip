@@ -9,7 +9,7 @@
 // THE GRID.  Cell edge = the smallest power of two >= the largest positive tolerance, so the 27-cell probe of
 // neighbours.hip (its header carries the proof; tolerances here are >= 2^-10, far above its 2^-60) cannot miss an edge
 // of any class.  Points are sorted by cell key, then stably by group = scan * 64 + class (not live: group 2048, last),
-// so a group is one cell-ordered segment and the nine range look-ups of a probe stay inside it.
+// so a group is one cell-ordered segment and the nine range look-ups of a probe (run_bound of cellsort.h) stay inside it.
 //
 // THE UNION.  One wave per live point: its lanes stride over the candidates of a cell run (coalesced 16-byte records),
 // and every lane whose candidate has a SMALLER original row and passes the predicate unites the two rows in a
@@ -21,47 +21,29 @@
 // walks descend strictly across retries -- and a thread that runs out, or reads a parent outside [0, x], raises the
 // status word and leaves.
 //
-// THE TABLES.  Flatten (root per row, sizes by integer atomicAdd at the root), flag the kept roots, one flag scan = ids in
-// ascending root order, inst, one stable sort of (id, row) = members, heads of the sorted ids = member_ptr, one wave
-// per instance = class and box (min / max: exact, order-free).  Integer atomics only, vector stores only.
-#include <cmath>
-
+// THE TABLES.  Flatten (root per row, sizes by integer atomicAdd at the root), flag the kept roots, one flag scan
+// (tiled_scan of scan.h) = ids in ascending root order, inst, one stable sort of (id, row) = members, heads of the
+// sorted ids = member_ptr, one wave per instance = class and box (min / max: exact, order-free).  Integer atomics only,
+// vector stores only.
+#include "cellsort.h"
 #include "common.h"
 #include "grid.h"
 #include "scan.h"
 
 using namespace lidal;
 using namespace lidal::grid;
+using namespace lidal::cellsort;
 
 namespace {
 
 constexpr int EC_BLOCK = 256;
 constexpr int EC_WAVES = EC_BLOCK / kWave;
-constexpr int EC_MAX_BLOCKS = 1 << 20;             // the wave-per-item launches are grid-stride loops
-constexpr int EC_SCAN_ITEMS = 8;
-constexpr int EC_SCAN_TILE = EC_BLOCK * EC_SCAN_ITEMS;
 constexpr int EC_CLASSES = 64;
 constexpr int EC_MAX_SCANS = 32;
 constexpr unsigned EC_DEAD = EC_MAX_SCANS * EC_CLASSES;         // the group of a point that is not live: sorts last
 constexpr int EC_GROUP_BITS = 12;
 constexpr int EC_GPTR = EC_DEAD + 2;               // gptr[g] = where group g begins, g = 0 .. EC_DEAD + 1
-constexpr int64_t kFieldMax = (1ll << kCellBits) - 1;
 constexpr int ST_ERR = 0, ST_PTR = 1;              // status words (include/lidal_amd.h)
-
-typedef unsigned long long u64;
-
-struct __attribute__((aligned(16))) PointRec { float x, y, z; int idx; };
-
-__device__ __forceinline__ void raise(long long* status, int word) { atomicMax((u64*)&status[ST_ERR], (u64)word); }
-
-// the expression of within() in neighbours.hip
-__device__ __forceinline__ bool within(const PointRec& a, const PointRec& b, float radius) {
-  const float dx = __fsub_rn(a.x, b.x), dy = __fsub_rn(a.y, b.y), dz = __fsub_rn(a.z, b.z);
-  const float s = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-  return sqrtf(s) < radius;
-}
-
-__device__ __forceinline__ bool finite_f32(float v) { return fabsf(v) <= 3.402823466e38f; }      // false for NaN
 
 // ---------------------------------------------------------------- keys, groups, records
 // per point: its group, the key of its cell (the parking cell unless live and in range), itself as the sort's
@@ -83,13 +65,8 @@ __global__ void __launch_bounds__(EC_BLOCK) ec_keys_kernel(const float* __restri
     if (ix == -kBias || iy == -kBias || iz == -kBias) {
       raise(status, LIDAL_CLUSTERS_CELL_RANGE);     // parked with the points that are not live: the launches stay in bounds
     } else {
-      int lo = 0, hi = n_scans;                     // the last s with point_ptr[s] <= i
-      for (int it = 0; it < 32 && hi - lo > 1; ++it) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (point_ptr[mid] <= i) lo = mid; else hi = mid;
-      }
       k = cell_key(ix, iy, iz);
-      g = (unsigned)lo * EC_CLASSES + (unsigned)lab;
+      g = (unsigned)segment_of(point_ptr, n_scans, i) * EC_CLASSES + (unsigned)lab;
     }
   }
   key[i] = k;
@@ -103,19 +80,6 @@ __global__ void __launch_bounds__(EC_BLOCK) ec_group_key_kernel(const int* __res
                                                                 int64_t p, unsigned* __restrict__ key32) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q < p) key32[q] = gkey[sidx[q]];
-}
-
-// the points in (group, cell) order: one 16-byte record and the cell key each
-__global__ void __launch_bounds__(EC_BLOCK) ec_records_kernel(const float* __restrict__ xyz, int64_t p,
-                                                              const int* __restrict__ sidx, const u64* __restrict__ key,
-                                                              PointRec* __restrict__ rec, u64* __restrict__ skey) {
-  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= p) return;
-  const int64_t j = sidx[q];
-  PointRec r;
-  r.x = xyz[j * 3 + 0]; r.y = xyz[j * 3 + 1]; r.z = xyz[j * 3 + 2]; r.idx = (int)j;
-  rec[q] = r;
-  skey[q] = key[j];
 }
 
 // gptr[g] = the first sorted position whose group is >= g, g = 0 .. EC_DEAD + 1: at most 32 halvings each
@@ -170,45 +134,24 @@ __device__ __forceinline__ bool unite(int* parent, int a, int b, int64_t p) {
   }
 }
 
-// first position in the ascending keys[lo, hi) whose key is >= target: at most 32 halvings
-__device__ __forceinline__ int lower_bound(const u64* __restrict__ keys, int lo, int hi, u64 target) {
-  for (int it = 0; it < 32 && lo < hi; ++it) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < target) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ void __launch_bounds__(EC_BLOCK)
-ec_union_kernel(const u64* __restrict__ skey, const unsigned* __restrict__ sgroup, const PointRec* __restrict__ rec,
+ec_union_kernel(const u64* __restrict__ skey, const unsigned* __restrict__ sgroup, const Rec* __restrict__ rec,
                 const int* __restrict__ gptr, const float* __restrict__ tol, int64_t p, int* parent, long long* status) {
   const int lane = lane_id();
   const int64_t n_live = gptr[EC_DEAD];             // the live points come first
   for (int64_t q = (int64_t)blockIdx.x * EC_WAVES + (threadIdx.x >> 6); q < n_live; q += (int64_t)gridDim.x * EC_WAVES) {
     const u64 key = skey[q];                        // (q, and everything derived from it alone, is uniform in the wave)
     const unsigned g = sgroup[q];
-    const PointRec me = rec[q];
+    const Rec me = rec[q];
     if (g >= EC_DEAD || key == 0) continue;         // (cannot be: a live point has a group and a cell)
     const float radius = tol[g & (EC_CLASSES - 1)];
     const int seg_lo = gptr[g], seg_hi = gptr[g + 1];
-    int64_t cx, cy, cz;
-    cell_unpack(key, &cx, &cy, &cz);
-    // lanes 0..8: where run (dx, dy) begins; lanes 9..17: where it ends (neighbours.hip: field values 1 .. 2^21 - 1 only)
-    int bound = seg_lo;
-    if (lane < 18) {
-      const int r = lane < 9 ? lane : lane - 9;
-      const int64_t fx = cx + kBias + (r / 3 - 1), fy = cy + kBias + (r % 3 - 1), fz = cz + kBias;
-      if (fx >= 1 && fx <= kFieldMax && fy >= 1 && fy <= kFieldMax) {
-        const int64_t z0 = fz - 1 >= 1 ? fz - 1 : 1, z1 = fz + 1 <= kFieldMax ? fz + 1 : kFieldMax;
-        const u64 xy = ((u64)fx << (2 * kCellBits)) | ((u64)fy << kCellBits);
-        bound = lower_bound(skey, seg_lo, seg_hi, lane < 9 ? (xy | (u64)z0) : (xy | (u64)z1) + 1);
-      }
-    }
+    const int bound = run_bound(skey, seg_lo, seg_hi, key, lane);    // lanes 0..8: a run begins; 9..17: it ends
     bool ok = true;
     for (int r = 0; r < 9; ++r) {
       const int lo = __shfl(bound, r), hi = __shfl(bound, r + 9);
       for (int64_t t = (int64_t)lo + lane; t < hi; t += kWave) {
-        const PointRec o = rec[t];
+        const Rec o = rec[t];
         if (o.idx < me.idx && within(me, o, radius)) ok = unite(parent, me.idx, o.idx, p) && ok;
       }
     }
@@ -243,55 +186,6 @@ __global__ void __launch_bounds__(EC_BLOCK) ec_flag_kernel(const int* __restrict
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p) return;
   flag[i] = (root[i] == (int)i && size[i] >= min_points && size[i] <= max_points) ? 1 : 0;
-}
-
-// inclusive scan of 0/1 flags: tile sums, their scan by scan.h's one-workgroup kernel, the tiles again
-__device__ __forceinline__ int block_exclusive(int v, int* wave_sum, int* total) {
-  const int lane = lane_id(), wave = threadIdx.x >> 6;
-  int incl = v;
-  for (int d = 1; d < kWave; d <<= 1) {
-    const int t = __shfl_up(incl, d, kWave);
-    if (lane >= d) incl += t;
-  }
-  if (lane == kWave - 1) wave_sum[wave] = incl;
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int w = 0; w < EC_WAVES; ++w) {
-    const int c = wave_sum[w];
-    if (w < wave) off += c;
-    tot += c;
-  }
-  __syncthreads();
-  if (total != nullptr) *total = tot;
-  return off + incl - v;
-}
-
-__global__ void __launch_bounds__(EC_BLOCK) ec_scan_sums_kernel(const int* __restrict__ flag, int64_t n,
-                                                                int* __restrict__ sums) {
-  __shared__ int sh[EC_WAVES];
-  const int64_t base = (int64_t)blockIdx.x * EC_SCAN_TILE + (int64_t)threadIdx.x * EC_SCAN_ITEMS;
-  int mine = 0;
-  for (int j = 0; j < EC_SCAN_ITEMS; ++j)
-    if (base + j < n) mine += flag[base + j];
-  int total;
-  block_exclusive(mine, sh, &total);
-  if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(EC_BLOCK) ec_scan_apply_kernel(const int* __restrict__ flag, int64_t n,
-                                                                 const int64_t* __restrict__ offs, int* __restrict__ incl) {
-  __shared__ int sh[EC_WAVES];
-  const int64_t base = (int64_t)blockIdx.x * EC_SCAN_TILE + (int64_t)threadIdx.x * EC_SCAN_ITEMS;
-  int f[EC_SCAN_ITEMS], mine = 0;
-  for (int j = 0; j < EC_SCAN_ITEMS; ++j) {
-    f[j] = base + j < n ? flag[base + j] : 0;
-    mine += f[j];
-  }
-  int run = (int)offs[blockIdx.x] + block_exclusive(mine, sh, nullptr);
-  for (int j = 0; j < EC_SCAN_ITEMS; ++j) {
-    run += f[j];
-    if (base + j < n) incl[base + j] = run;
-  }
 }
 
 // inst[i], the key of the members' sort (a point of no instance: p, behind every id), and, by the first n_scans + 1
@@ -379,12 +273,12 @@ struct ClusterWs {
   unsigned *gkey, *key32, *sgroup, *mkey, *smkey;
   int *idx_a, *idx_b, *idx_c, *parent, *root, *size, *flag, *incl, *sums;
   int64_t* offs;
-  PointRec* rec;
+  Rec* rec;
   char* sort;
   int64_t sort_bytes, total;
 };
 ClusterWs cluster_layout(int64_t p_total, int n_scans, void* ws) {
-  const int64_t p = p_total > 0 ? p_total : 1, ns = n_scans > 0 ? n_scans : 1, nb = cdiv(p, EC_SCAN_TILE);
+  const int64_t p = p_total > 0 ? p_total : 1, ns = n_scans > 0 ? n_scans : 1, nb = scan_tiles(p);
   const int64_t sb = radix_sort_ws_bytes(p, 8, true);
   Carver c(ws);
   ClusterWs w;
@@ -398,14 +292,12 @@ ClusterWs cluster_layout(int64_t p_total, int n_scans, void* ws) {
   w.parent = c.take<int>(p); w.root = c.take<int>(p); w.size = c.take<int>(p);
   w.flag = c.take<int>(p); w.incl = c.take<int>(p); w.sums = c.take<int>(nb);
   w.offs = c.take<int64_t>(nb + 1);
-  w.rec = c.take<PointRec>(p);
+  w.rec = c.take<Rec>(p);
   w.sort = c.take(sb);
   w.sort_bytes = sb;
   w.total = c.total();
   return w;
 }
-
-unsigned capped(int64_t blocks) { return (unsigned)(blocks < EC_MAX_BLOCKS ? blocks : EC_MAX_BLOCKS); }
 
 }  // namespace
 
@@ -438,9 +330,7 @@ extern "C" int lidal_euclidean_clusters(const float* xyz, const int64_t* labels,
   const ClusterWs w = cluster_layout(P, n_scans, ws);
   LIDAL_REQUIRE(ws_bytes >= w.total, "euclidean_clusters: workspace too small");
   if (P == 0 || top == 0.f) return 0;               // no instance: nothing is launched, nothing is written
-  int e;
-  const double m = frexp((double)top, &e);          // top = m 2^e, m in [0.5, 1): the smallest power of two >= top
-  const double cell = m == 0.5 ? (double)top : ldexp(1.0, e);
+  const double cell = cell_edge(top);
 
   hipStream_t s = (hipStream_t)stream;
   long long* st = (long long*)status;
@@ -457,7 +347,7 @@ extern "C" int lidal_euclidean_clusters(const float* xyz, const int64_t* labels,
   ec_group_key_kernel<<<grid, EC_BLOCK, 0, s>>>(w.idx_b, w.gkey, P, w.key32);
   LIDAL_CHECK_LAUNCH("clusters_group_key");
   if (int rc = radix_sort(w.key32, w.idx_b, w.sgroup, w.idx_c, P, 4, EC_GROUP_BITS, w.sort, w.sort_bytes, s)) return rc;
-  ec_records_kernel<<<grid, EC_BLOCK, 0, s>>>(xyz, P, w.idx_c, w.key, w.rec, w.gskey);
+  records_kernel<true><<<grid, EC_BLOCK, 0, s>>>(xyz, P, w.idx_c, w.key, w.rec, w.gskey);
   LIDAL_CHECK_LAUNCH("clusters_records");
   ec_group_ptr_kernel<<<(unsigned)cdiv(EC_GPTR, EC_BLOCK), EC_BLOCK, 0, s>>>(w.sgroup, P, w.gptr);
   LIDAL_CHECK_LAUNCH("clusters_group_ptr");
@@ -469,13 +359,7 @@ extern "C" int lidal_euclidean_clusters(const float* xyz, const int64_t* labels,
   LIDAL_CHECK_LAUNCH("clusters_flatten");
   ec_flag_kernel<<<grid, EC_BLOCK, 0, s>>>(w.root, w.size, P, min_points, max_points, w.flag);
   LIDAL_CHECK_LAUNCH("clusters_flag");
-  const int nb = (int)cdiv(P, EC_SCAN_TILE);
-  ec_scan_sums_kernel<<<(unsigned)nb, EC_BLOCK, 0, s>>>(w.flag, P, w.sums);
-  LIDAL_CHECK_LAUNCH("clusters_scan_sums");
-  scan_counts_kernel<<<1, 1024, 0, s>>>(w.sums, nb, w.offs);
-  LIDAL_CHECK_LAUNCH("clusters_scan_top");
-  ec_scan_apply_kernel<<<(unsigned)nb, EC_BLOCK, 0, s>>>(w.flag, P, w.offs, w.incl);
-  LIDAL_CHECK_LAUNCH("clusters_scan_apply");
+  if (int rc = tiled_scan<int, true, false>(w.flag, P, w.sums, w.offs, w.incl, s)) return rc;
   ec_inst_kernel<<<(unsigned)cdiv(P > n_scans ? P : n_scans + 1, EC_BLOCK), EC_BLOCK, 0, s>>>(
       w.root, w.flag, w.incl, P, w.point_ptr, n_scans, inst, w.mkey, w.idx_a, st);
   LIDAL_CHECK_LAUNCH("clusters_inst");

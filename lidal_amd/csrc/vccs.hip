@@ -11,108 +11,32 @@
 // All frames of a batch advance in the same launches: voxels, seed cells and supervoxels are numbered across the
 // batch, frame after frame, and the grids run over their bound (the batch's points).  Their counts stay on the device
 // (status[1..3]); a thread beyond the live count leaves.  Every loop has a bound known at launch; a state that should
-// be impossible writes an error word (status[0]) that the wrapper raises from.
+// be impossible writes an error word (status[0]) that the wrapper raises from.  The scans of the flags are scan.h's
+// tiled_scan; the look-ups by key and by frame and the error word are cellsort.h's (lower_bound, segment_of, raise).
 #include <math.h>
 
+#include "cellsort.h"
 #include "common.h"
 #include "grid.h"
+#include "scan.h"
 #include "sym3.h"
 
 using namespace lidal;
 using namespace lidal::grid;
+using namespace lidal::cellsort;
 using namespace lidal::sym3;
 
 namespace {
 
 constexpr int VC_BLOCK = 256;
-constexpr int SCAN_ITEMS = 8;
-constexpr int SCAN_TILE = VC_BLOCK * SCAN_ITEMS;       // flags per block of the scan
 constexpr int LABEL_BITS = 24;                         // a label is at most the frame's voxels, below 2^24
 // status words (include/lidal_amd.h)
 constexpr int ST_ERR = 0, ST_V = 1, ST_G = 2, ST_S = 3, ST_PTR = 4;
 
-typedef unsigned long long u64;
-
-__device__ __forceinline__ void raise(long long* status, int word) { atomicMax((u64*)&status[ST_ERR], (u64)word); }
-
-// position of `key` among the ascending keys[lo, hi), or -1: at most 32 halvings
+// position of `key` among the ascending keys[lo, hi), or -1
 __device__ __forceinline__ int find_key(const u64* __restrict__ keys, int lo, int hi, u64 key) {
-  const int end = hi;
-  for (int it = 0; it < 32 && lo < hi; ++it) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return (lo < end && keys[lo] == key) ? lo : -1;
-}
-
-// ---------------------------------------------------------------- inclusive scan of 0/1 flags, three launches
-__device__ __forceinline__ int block_exclusive(int v, int* sh, int* total) {
-  const int tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (int o = 1; o < VC_BLOCK; o <<= 1) {
-    const int t = tid >= o ? sh[tid - o] : 0;
-    __syncthreads();
-    sh[tid] += t;
-    __syncthreads();
-  }
-  const int incl = sh[tid];
-  if (total != nullptr) *total = sh[VC_BLOCK - 1];
-  __syncthreads();
-  return incl - v;
-}
-
-__global__ void __launch_bounds__(VC_BLOCK) scan_sums_kernel(const int* __restrict__ flags, int64_t n,
-                                                             int* __restrict__ sums) {
-  __shared__ int sh[VC_BLOCK];
-  const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
-  int mine = 0;
-  for (int j = 0; j < SCAN_ITEMS; ++j)
-    if (base + j < n) mine += flags[base + j];
-  int total;
-  block_exclusive(mine, sh, &total);
-  if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// sums[nb] -> their exclusive scan in place, by one block: ceil(nb / 256) steps
-__global__ void __launch_bounds__(VC_BLOCK) scan_top_kernel(int* __restrict__ sums, int nb) {
-  __shared__ int sh[VC_BLOCK];
-  int carry = 0;
-  for (int base = 0; base < nb; base += VC_BLOCK) {
-    const int i = base + (int)threadIdx.x;
-    const int v = i < nb ? sums[i] : 0;
-    int total;
-    const int ex = block_exclusive(v, sh, &total);
-    if (i < nb) sums[i] = carry + ex;
-    carry += total;
-  }
-}
-
-__global__ void __launch_bounds__(VC_BLOCK) scan_apply_kernel(const int* __restrict__ flags, int64_t n,
-                                                              const int* __restrict__ sums, int* __restrict__ incl) {
-  __shared__ int sh[VC_BLOCK];
-  const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
-  int f[SCAN_ITEMS], mine = 0;
-  for (int j = 0; j < SCAN_ITEMS; ++j) {
-    f[j] = base + j < n ? flags[base + j] : 0;
-    mine += f[j];
-  }
-  int run = sums[blockIdx.x] + block_exclusive(mine, sh, nullptr);
-  for (int j = 0; j < SCAN_ITEMS; ++j) {
-    run += f[j];
-    if (base + j < n) incl[base + j] = run;
-  }
-}
-
-int scan_flags(const int* flags, int64_t n, int* sums, int* incl, hipStream_t s) {
-  const int nb = (int)cdiv(n, SCAN_TILE);
-  scan_sums_kernel<<<(unsigned)nb, VC_BLOCK, 0, s>>>(flags, n, sums);
-  LIDAL_CHECK_LAUNCH("vccs_scan_sums");
-  scan_top_kernel<<<1, VC_BLOCK, 0, s>>>(sums, nb);
-  LIDAL_CHECK_LAUNCH("vccs_scan_top");
-  scan_apply_kernel<<<(unsigned)nb, VC_BLOCK, 0, s>>>(flags, n, sums, incl);
-  LIDAL_CHECK_LAUNCH("vccs_scan_apply");
-  return 0;
+  const int at = lower_bound(keys, lo, hi, key);
+  return (at < hi && keys[at] == key) ? at : -1;
 }
 
 // ---------------------------------------------------------------- points -> voxels
@@ -123,12 +47,7 @@ __global__ void __launch_bounds__(VC_BLOCK) point_key_kernel(const float* __rest
                                                              int* __restrict__ iota, long long* status) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p) return;
-  int lo = 0, hi = n_frames;                           // the last f with frame_ptr[f] <= i
-  for (int it = 0; it < 32 && hi - lo > 1; ++it) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (frame_ptr[mid] <= i) lo = mid; else hi = mid;
-  }
-  pframe[i] = lo;
+  pframe[i] = segment_of(frame_ptr, n_frames, i);
   iota[i] = (int)i;
   const double x = (double)xyz[i * 3 + 0], y = (double)xyz[i * 3 + 1], z = (double)xyz[i * 3 + 2];
   uint64_t k = 0;
@@ -509,6 +428,7 @@ struct VccsWs {
   u64 *key, *skey, *vkey, *gmin;
   unsigned *key32, *skey32;
   int *idx_a, *idx_b, *idx_c, *pframe, *vframe, *flag, *incl, *sums, *nbr, *vseg, *gcand, *gcount, *owner;
+  int64_t* offs;
   long long *qv, *qn, *acc;
   double *sd2, *dist, *svc, *svn;
   char* sort;
@@ -525,7 +445,8 @@ VccsWs vccs_layout(int64_t p_total, int n_frames, void* ws) {
   w.key32 = c.take<unsigned>(p); w.skey32 = c.take<unsigned>(p);
   w.idx_a = c.take<int>(p); w.idx_b = c.take<int>(p); w.idx_c = c.take<int>(p);
   w.pframe = c.take<int>(p); w.vframe = c.take<int>(p);
-  w.flag = c.take<int>(p); w.incl = c.take<int>(p); w.sums = c.take<int>(cdiv(p, SCAN_TILE) + 1);
+  w.flag = c.take<int>(p); w.incl = c.take<int>(p);
+  w.sums = c.take<int>(scan_tiles(p)); w.offs = c.take<int64_t>(scan_tiles(p) + 1);
   w.nbr = c.take<int>(27 * p);
   w.vseg = c.take<int>(p); w.gcand = c.take<int>(p); w.gcount = c.take<int>(p);
   w.owner = c.take<int>(2 * p);
@@ -604,7 +525,7 @@ extern "C" int lidal_vccs(const float* xyz, const int64_t* frame_ptr_host, int n
   if (int rc = sort_by_frame_key(w, w.pframe, P, n_frames, fbits, nullptr, &sorted, s)) return rc;
   head_kernel<<<grid, VC_BLOCK, 0, s>>>(sorted, w.pframe, w.key, P, nullptr, w.flag);
   LIDAL_CHECK_LAUNCH("vccs_head");
-  if (int rc = scan_flags(w.flag, P, w.sums, w.incl, s)) return rc;
+  if (int rc = tiled_scan<int, true, false>(w.flag, P, w.sums, w.offs, w.incl, s)) return rc;
   voxel_fill_kernel<<<grid, VC_BLOCK, 0, s>>>(xyz, P, n_frames, sorted, w.pframe, w.key, w.flag, w.incl, point_voxel,
                                               w.vkey, w.vframe, (long long*)qs, nv, st);
   LIDAL_CHECK_LAUNCH("vccs_voxel_fill");
@@ -621,7 +542,7 @@ extern "C" int lidal_vccs(const float* xyz, const int64_t* frame_ptr_host, int n
   if (int rc = sort_by_frame_key(w, w.vframe, P, n_frames, fbits, st + ST_V, &sorted, s)) return rc;
   head_kernel<<<grid, VC_BLOCK, 0, s>>>(sorted, w.vframe, w.key, P, st + ST_V, w.flag);
   LIDAL_CHECK_LAUNCH("vccs_seed_head");
-  if (int rc = scan_flags(w.flag, P, w.sums, w.incl, s)) return rc;
+  if (int rc = tiled_scan<int, true, false>(w.flag, P, w.sums, w.offs, w.incl, s)) return rc;
   seed_cell_kernel<<<grid, VC_BLOCK, 0, s>>>(P, n_frames, st, sorted, w.vframe, w.flag, w.incl, w.vseg, w.gptr);
   LIDAL_CHECK_LAUNCH("vccs_seed_cell");
   seed_min_kernel<<<grid, VC_BLOCK, 0, s>>>(P, st, w.vseg, w.sd2, w.gmin);
@@ -632,7 +553,7 @@ extern "C" int lidal_vccs(const float* xyz, const int64_t* frame_ptr_host, int n
   LIDAL_CHECK_LAUNCH("vccs_seed_count");
   seed_flag_kernel<<<grid, VC_BLOCK, 0, s>>>(P, st, w.gcount, min_seed, w.flag);
   LIDAL_CHECK_LAUNCH("vccs_seed_flag");
-  if (int rc = scan_flags(w.flag, P, w.sums, w.incl, s)) return rc;
+  if (int rc = tiled_scan<int, true, false>(w.flag, P, w.sums, w.offs, w.incl, s)) return rc;
   seed_fill_kernel<<<grid, VC_BLOCK, 0, s>>>(P, n_frames, st, w.gptr, w.vframe, w.gcand, w.flag, w.incl, seed_voxels);
   LIDAL_CHECK_LAUNCH("vccs_seed_fill");
   // ---- state and rounds

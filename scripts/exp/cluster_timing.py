@@ -89,7 +89,7 @@ def profiled(fn):
                 g = 'copies_memsets'
             elif 'ec_union' in name:
                 g = 'union'
-            elif 'ec_' in name or 'scan_counts' in name:
+            elif any(t in name for t in ('ec_', 'scan_counts', 'scan_tile', 'records_kernel')):
                 g = 'keys_records_tables'
             elif 'at::' in name or 'elementwise' in name or 'cat' in name:
                 g = 'torch'

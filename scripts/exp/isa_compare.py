@@ -35,7 +35,8 @@ def kernels_of(tree, unit, tmp):
         meta = re.search(r'\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel' % re.escape(name), text, re.S)
         if meta is None:
             continue                                  # a device function, not a kernel
-        ins = [ln.split(';')[0].strip() for ln in body.split('\n')]
+        # (a branch target carries the function's number in the unit, which moves when a kernel becomes a template)
+        ins = [re.sub(r'\.LBB\d+_', '.LBB_', ln.split(';')[0].strip()) for ln in body.split('\n')]
         ins = [ln for ln in ins if ln and not ln.startswith('.') and not ln.endswith(':')]
         tail = text[m.end():m.end() + 4000]
         get = lambda key: int(re.search(r'; %s: (\d+)' % key, tail).group(1))

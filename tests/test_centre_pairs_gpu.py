@@ -153,6 +153,23 @@ def test_other_radii(radius, box):
     _check(c, radius)
 
 
+@pytest.mark.parametrize('n', [2047, 2048, 2049, 524288, 524289, 2097153])
+def test_lattice_at_the_edges_of_the_scan(n):
+    """Sizes chosen for the scan of the row lengths (8 x 256 = 2048 lengths per tile): one tile and its neighbours, one
+    256-wide step of tile sums (256 x 2048) and one more, and one element past 1024 tiles.  Centres on a 1 m lattice,
+    4096 to a row, radius 1.25 m: the neighbours of i are i - 4096, i - 1, i + 1, i + 4096 where they exist, so the
+    lengths are 2, 3 or 4 and the table is index arithmetic.  Every value is exact in f32; the cell edge is 2 m."""
+    from lidal_amd.score import centre_pairs
+    i = np.arange(n, dtype=np.int64)
+    centers = np.stack([i % 4096, i // 4096, np.zeros(n, np.int64)], axis=1).astype(np.float32)
+    cand = np.stack([i - 4096, i - 1, i + 1, i + 4096], axis=1)
+    there = np.stack([i >= 4096, i % 4096 != 0, (i % 4096 != 4095) & (i + 1 < n), i + 4096 < n], axis=1)
+    row_ptr, col = centre_pairs(centers, 1.25)
+    assert row_ptr.dtype == np.int64 and col.dtype == np.int32
+    assert np.array_equal(row_ptr, np.concatenate([[0], np.cumsum(there.sum(axis=1))]))
+    assert np.array_equal(col, cand[there].astype(np.int32))
+
+
 def test_radius_float32_cannot_hold_is_refused():
     from lidal_amd.score import centre_pairs
     with pytest.raises(ValueError):

@@ -210,6 +210,28 @@ def test_size_filters():
     assert got.inst_ptr.tolist() == [0, 1, 2]
 
 
+@pytest.mark.parametrize('p', [2047, 2048, 2049, 524289, 2097153])
+def test_pairs_on_a_lattice_at_the_edges_of_the_scan(p):
+    """Sizes chosen for the scan of the kept-root flags (8 x 256 = 2048 flags per tile): one tile and its neighbours, one
+    element past 256 tiles and one past 1024.  Sites on a 1 m lattice, 1024 to a row; a site holds two points 0.1 m
+    apart, every third site a single point; rows in site order, cut at p.  One class, tolerance 0.25 m, min_points 2:
+    the flags run 1, 0, 1, 0, 0, ... and instance k is the k-th whole pair, so every table is index arithmetic."""
+    i = np.arange(p, dtype=np.int64)
+    r = i % 5                                           # rows 0, 1 and 2, 3 of a period are pairs, row 4 stands alone
+    site = 3 * (i // 5) + np.array([0, 0, 1, 1, 2])[r]
+    xyz = np.stack([(site % 1024).astype(np.float32) + np.where((r == 1) | (r == 3), np.float32(0.1), F0),
+                    (site // 1024).astype(np.float32), np.zeros(p, np.float32)], axis=1).astype(np.float32)
+    first = np.flatnonzero(((r == 0) | (r == 2)) & (i + 1 < p))
+    k = len(first)
+    inst = np.full(p, -1, np.int32)
+    inst[first] = inst[first + 1] = np.arange(k, dtype=np.int32)
+    want = dict(inst=inst, inst_ptr=np.array([0, k], np.int64), cls=np.zeros(k, np.int32),
+                member_ptr=2 * np.arange(k + 1, dtype=np.int64),
+                members=np.stack([first, first + 1], axis=1).reshape(-1).astype(np.int32),
+                bbox=np.concatenate([xyz[first], xyz[first + 1]], axis=1), sizes=np.full(k, 2, np.int64))
+    _same(_run([xyz], tolerance=0.25, min_points=2), want)
+
+
 def test_order_permutation_and_repetition(scene):
     got = _run_scene(scene)
     first = got.members[got.member_ptr[:-1]]

@@ -87,6 +87,25 @@ def test_voxels_and_normals_equal_the_restatement_bit_for_bit(name):
     assert len(diff) == 0, (name, diff[:5], got[diff[:5]], nrm[diff[:5]])
 
 
+@pytest.mark.parametrize('p,side', [(2047, 8), (2048, 8), (2049, 8), (524289, 32)])
+def test_random_scans_at_the_edges_of_the_scan(p, side):
+    """Sizes chosen for the scans of the head flags (8 x 256 = 2048 flags per tile): one tile and its neighbours, and one
+    element past 256 tiles.  A seeded random ground patch of 2 side x 2 side metres against the whole restatement, every
+    array (the restatement takes about 0.1 s on the small scans and 2 s on the large one: 16 397 voxels, 64 seeds)."""
+    from lidal_amd import data
+    rng = np.random.RandomState(p)
+    xyz = np.stack([rng.uniform(-side, side, p), rng.uniform(-side, side, p), rng.normal(-1.7, 0.05, p)],
+                   axis=1).astype(np.float32)
+    want = R.vccs(xyz)
+    labels, _, _, det = data.vccs_supervoxels(_dev(xyz), details=True)
+    assert len(want['seed_voxels']) >= 4 and len(want['cells']) > 800
+    assert np.array_equal(labels.cpu().numpy(), want['labels'])
+    for key in ('point_voxel', 'cells', 'qs', 'n', 'seed_voxels', 'owners'):
+        assert np.array_equal(det[key].cpu().numpy(), want[key]), key
+    for key in ('centroids', 'normals'):
+        assert np.array_equal(_bits(det[key].cpu().numpy()), _bits(want[key])), key
+
+
 def test_flat_plane_is_four_supervoxels_of_400_voxels():
     owners = _run('flat_plane')[3]['owners'].cpu().numpy()
     assert np.array_equal(np.bincount(owners), [0, 400, 400, 400, 400])
