@@ -880,6 +880,40 @@ int lidal_euclidean_clusters(const float* xyz, const int64_t* labels, int64_t p,
                              int32_t* cls, int64_t* member_ptr, int32_t* members, float* bbox, int64_t* status, void* ws,
                              int64_t ws_bytes, void* stream);
 
+/* ---- panoptic quality: predicted instances scored against annotated ones (csrc/panoptic.hip) ---- */
+/* The per-class sums behind PQ = SQ x RQ, added into accumulators that live on the device across calls.  n_scans
+ * (1..32) scans laid end to end, point_ptr i64 [n_scans + 1] on the HOST (ascending from 0 to p < 2^30); per row
+ * pred_sem, gt_sem i64 [p] and pred_inst, gt_inst i32 [p] on the device; c in 1..64 classes; bit k of `things` set iff
+ * class k has instances (no bit at or above c); min_points >= 1.
+ *   A row is VOID iff gt_sem is outside [0, c); void rows take part in nothing.  A non-void row has a predicted segment
+ *   iff pred_sem is in [0, c).  A segment is (scan, class, id): id = 0 for a stuff class whatever the instance column
+ *   holds, id = inst + 1 for a thing class (inst = -1 is the class's one unassigned segment of the scan).  Equal ids in
+ *   different scans are different segments.  An instance value of a thing row lies in [-1, 2^30 - 2]: a gt_inst outside
+ *   makes the row void, a pred_inst outside leaves it without a predicted segment, either raises LIDAL_PANOPTIC_BAD_ID.
+ *   area = the non-void rows of a segment; inter = the rows in both a gt and a predicted segment of one class;
+ *   union = area_gt + area_pred - inter.  The pair MATCHES iff 2 * inter > union in integers -- which is
+ *   inter / union > 0.5 in f64 for every union below 2^30: 2 * inter > union gives a quotient of at least
+ *   0.5 + 1 / (2 union) > 0.5 + 2^-31, far above one rounding; 2 * inter <= union gives at most 0.5 exactly.  A segment
+ *   has at most one match: a match holds more than half of the segment's rows, the partners of one segment are disjoint
+ *   subsets of it, and two disjoint subsets cannot each hold more than half.
+ * Per call and class k:  tp[k] += matches;  fn[k] += gt segments with area >= min_points and no match;
+ * fp[k] += predicted segments with area >= min_points and no match;  iou[k] = iou[k] + part[k], part[k] = +0.0 plus
+ * (double)inter / (double)union (the correctly rounded IEEE division) of the class's matches, added one by one in
+ * ascending (scan, gt id).  No float atomics: the result is a function of the input alone, and a permutation of the
+ * rows inside a scan gives the same 64 bits.
+ *   tp, fp, fn i64 [c], iou f64 [c], status i64 [1] (word 0: 0 or a LIDAL_PANOPTIC_ word; it only grows): on the
+ *   device, zeroed once by the caller, updated in place by every call.
+ * p = 0 returns 0 and launches nothing.  Refusals (c, n_scans, min_points, point_ptr, things, the workspace) come before
+ * the first launch.  Does not synchronise the stream.  Workspace: lidal_panoptic_accumulate_workspace_bytes(p, n_scans). */
+enum {
+  LIDAL_PANOPTIC_BAD_ID = 1  /* an instance value of a thing row outside [-1, 2^30 - 2] */
+};
+int64_t lidal_panoptic_accumulate_workspace_bytes(int64_t p, int n_scans);
+int lidal_panoptic_accumulate(const int64_t* pred_sem, const int32_t* pred_inst, const int64_t* gt_sem,
+                              const int32_t* gt_inst, int64_t p, const int64_t* point_ptr_host, int n_scans, int c,
+                              uint64_t things, int64_t min_points, int64_t* tp, int64_t* fp, int64_t* fn, double* iou,
+                              int64_t* status, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- ReDAL region selection (score/sv_level/ReDAL.py, dataset/ReDAL/gen_surface_variation_sk.py; csrc/redal.hip) ---- */
 /* k nearest OTHER points of every point of a raw scan xyz f32 [p,3]: knn i32 [p,k], sorted by (f64 distance, index).
  * 1 <= k <= 64; p < k + 1 is refused (status 2, lidal_last_error).  `cell`: the search grid's cell in metres (the

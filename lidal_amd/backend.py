@@ -167,6 +167,9 @@ SIGNATURES = {
     'lidal_radius_pairs_fill': (_i32, [_vp, _i64, _f32, _vp, _vp, _vp, _i64, _vp]),
     'lidal_euclidean_clusters_workspace_bytes': (_i64, [_i64, _i32]),
     'lidal_euclidean_clusters': (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'lidal_panoptic_accumulate_workspace_bytes': (_i64, [_i64, _i32]),
+    'lidal_panoptic_accumulate': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, ctypes.c_uint64, _i64, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _i64, _vp]),
     'lidal_knn_workspace_bytes': (_i64, [_i64]),
     'lidal_knn': (_i32, [_vp, _i64, _i32, _f64, _vp, _vp, _i64, _vp]),
     'lidal_surface_variation': (_i32, [_vp, _i64, _i32, _f64, _f32, _vp, _vp, _i64, _vp]),

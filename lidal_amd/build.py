@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(CSRC, '_obj')
 LIB = os.path.join(HERE, 'liblidal_amd.so')
-SOURCES = ['error.cpp', 'hash.hip', 'kmap.hip', 'voxel.hip', 'conv.hip', 'conv_img.hip', 'wgrad_dma.hip', 'wgrad_streams.hip', 'sort.hip', 'bn.hip', 'elementwise.hip', 'score.hip', 'plan.hip', 'redal.hip', 'kmeans.hip', 'frame_level.hip', 'labels.hip', 'supervoxel.hip', 'vccs.hip', 'neighbours.hip', 'optim.hip', 'loss.hip', 'mix.hip', 'semi.hip', 'transfer.hip', 'icp.hip', 'dropout.hip', 'cluster.hip']
+SOURCES = ['error.cpp', 'hash.hip', 'kmap.hip', 'voxel.hip', 'conv.hip', 'conv_img.hip', 'wgrad_dma.hip', 'wgrad_streams.hip', 'sort.hip', 'bn.hip', 'elementwise.hip', 'score.hip', 'plan.hip', 'redal.hip', 'kmeans.hip', 'frame_level.hip', 'labels.hip', 'supervoxel.hip', 'vccs.hip', 'neighbours.hip', 'optim.hip', 'loss.hip', 'mix.hip', 'semi.hip', 'transfer.hip', 'icp.hip', 'dropout.hip', 'cluster.hip', 'panoptic.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wno-unused-result']
 # No packed-f32 VALU instructions (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32) in this library.  Measured on MI355X
 # (scripts/exp/victim/, profiles/README.md "A packed multiply beside v_mfma_f32_16x16x32_bf16"): while a wave of ANOTHER
@@ -23,7 +23,7 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wno-unused-res
 # exactly that form into ti_weights_kernel, and ~1 % of the points got a zero trilinear weight.
 NO_PACKED_F32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 # units that restate numpy arithmetic (separately rounded products and sums): no fma contraction
-NO_CONTRACT = {'score.hip', 'kmap.hip', 'redal.hip', 'kmeans.hip', 'frame_level.hip', 'supervoxel.hip', 'vccs.hip', 'neighbours.hip', 'optim.hip', 'loss.hip', 'mix.hip', 'semi.hip', 'transfer.hip', 'icp.hip', 'cluster.hip'}
+NO_CONTRACT = {'score.hip', 'kmap.hip', 'redal.hip', 'kmeans.hip', 'frame_level.hip', 'supervoxel.hip', 'vccs.hip', 'neighbours.hip', 'optim.hip', 'loss.hip', 'mix.hip', 'semi.hip', 'transfer.hip', 'icp.hip', 'cluster.hip', 'panoptic.hip'}
 
 
 def _stale(target, deps):

@@ -30,7 +30,9 @@ host and `mixed_train_batch` puts the step in front of voxelize_batch.
 Instances (the project's own definition): `euclidean_clusters` turns labels or predictions into
 instance ids -- the connected components of the fixed-radius graph per scan and class -- in lidal_euclidean_clusters
 with one read-back; `Instances.as_csr` hands a scan's instances to `train_labels` as regions, `draw_instance_paste`
-picks instances for a paste and `mix_scans(paste_masks=...)` pastes those rows only.
+picks instances for a paste and `mix_scans(paste_masks=...)` pastes those rows only.  `instance_ids` reads the annotated
+instances out of SemanticKITTI label words and `val_batch(with_instances=True)` carries them, with the raw points, to
+evaluate.evaluate_panoptic_batches.
 """
 import math
 
@@ -44,7 +46,8 @@ __all__ = ['draw_augmentation', 'voxelize_scan', 'collate', 'parse_calibration',
            'labeled_frames', 'frames_from_flag', 'kmeans_supervoxels', 'supervoxel_tables', 'balanced_assign',
            'supervoxel_bounds', 'supervoxel_costs', 'voxelize_batch', 'score_sample', 'mc_sample', 'val_batch', 'train_batch',
            'score_frame_inputs', 'class_weights', 'Mix', 'identity_mix', 'wedge_vectors', 'class_mask', 'draw_lasermix',
-           'draw_polarmix', 'mix_scans', 'mixed_train_batch', 'Instances', 'euclidean_clusters', 'draw_instance_paste']
+           'draw_polarmix', 'mix_scans', 'mixed_train_batch', 'Instances', 'euclidean_clusters', 'draw_instance_paste',
+           'instance_ids', 'SK_THINGS']
 
 SCALE = 20                # sk_dataset.py:56
 FULL_SCALE = 8192
@@ -125,6 +128,10 @@ IGNORE = 255              # train.py:136 ignore_index
 _SK_CLASS_IDS = (10, 11, 15, 18, 20, 30, 31, 32, 40, 44, 48, 49, 50, 51, 70, 71, 72, 80, 81)
 _SK_IGNORED_IDS = (0, 1, 13, 16, 52, 60, 99)     # unlabeled, outlier, bus, on-rails, other-structure, lane-marking, other-object
 _SK_MOVING = {252: 10, 253: 31, 254: 30, 255: 32, 256: 16, 257: 13, 258: 18, 259: 20}
+# the classes with annotated instances (the 'things' of the panoptic benchmark): car, bicycle, motorcycle, truck,
+# other-vehicle, person, bicyclist, motorcyclist -- as training classes, the other eleven being 'stuff'
+_SK_THING_IDS = (10, 11, 15, 18, 20, 30, 31, 32)
+SK_THINGS = tuple(_SK_CLASS_IDS.index(raw) for raw in _SK_THING_IDS)
 
 # nuScenes-lidarseg: the 32 annotated categories folded into the 16 classes of the lidarseg challenge, by class
 # (barrier, bicycle, bus, car, construction_vehicle, motorcycle, pedestrian, traffic_cone, trailer, truck,
@@ -224,6 +231,23 @@ def train_labels(raw_labels, label_map, sv_csr=None, sv_flag=None, pseudo=None, 
         return labels_p, labels_v, n_invalid
     check_labels(n_invalid)
     return labels_p, labels_v
+
+
+def instance_ids(raw_labels):
+    """The annotated instance ids of a SemanticKITTI scan: the upper 16 bits of its .label words (train_labels reads the
+    lower 16) as i32 [P] in 0..65535, on the tensor's device.  raw_labels: int32 or uint32 storage of the u32 words, a
+    tensor or a host array; a word with the top bit set is not sign-extended.  Ids are per scan and per class: 0 is
+    'no instance annotated', the id of stuff points."""
+    if not torch.is_tensor(raw_labels):
+        raw = np.ascontiguousarray(np.asarray(raw_labels))
+        if raw.dtype not in (np.int32, np.uint32):
+            raise TypeError('instance_ids: the label words must be int32 or uint32, not %s' % raw.dtype)
+        raw_labels = torch.from_numpy(raw.view(np.int32))
+    elif raw_labels.dtype == getattr(torch, 'uint32', None):
+        raw_labels = raw_labels.contiguous().view(torch.int32)
+    elif raw_labels.dtype != torch.int32:
+        raise TypeError('instance_ids: the label words must be int32 or uint32, not %s' % raw_labels.dtype)
+    return ((raw_labels.reshape(-1) >> 16) & 0xFFFF).to(torch.int32)      # the shift is arithmetic: the mask undoes it
 
 
 def check_labels(n_invalid):
@@ -371,16 +395,21 @@ def _batch_scans(scans, others, what):
     return scans
 
 
-def val_batch(scans, raw_labels, label_map, rng=np.random):
+def val_batch(scans, raw_labels, label_map, rng=np.random, with_instances=False):
     """The reference's validation batch (mode 'val' + collate_fn): scans is a list of (points, intensity) GPU pairs and
     raw_labels their annotation arrays (train_labels).  Draws per scan in order, one voxelize_batch, train_labels per
-    scan for labels_p, one check_labels -> the batch of evaluate_batches (labels_p_b beside inverse_indices_b)."""
+    scan for labels_p, one check_labels -> the batch of evaluate_batches (labels_p_b beside inverse_indices_b).
+    with_instances (SemanticKITTI label words): the batch of evaluate_panoptic_batches, which carries in addition
+    'points', the scans' raw f32 [P,3] rows, and 'gt_inst', instance_ids of every scan, as lists."""
     scans = _batch_scans(scans, [('label arrays', raw_labels)], 'val_batch')
     draws = [draw_augmentation(rng) for _ in scans]
     batch = voxelize_batch([x for x, _ in scans], [w for _, w in scans], [d[0] for d in draws], [d[1] for d in draws])
     out = [train_labels(raw, label_map, check=False) for raw in raw_labels]
     batch['labels_p_b'] = torch.cat([o[0] for o in out])
     check_labels([o[2] for o in out])
+    if with_instances:
+        batch['points'] = [x.float().contiguous() for x, _ in scans]
+        batch['gt_inst'] = [instance_ids(raw) for raw in raw_labels]
     return batch
 
 
