@@ -114,10 +114,17 @@ __global__ void __launch_bounds__(NT) bn_stats_partial_kernel(const T* __restric
   const int tid = threadIdx.x, cg = tid % cg_n, rl = tid / cg_n;
   const int64_t r_beg = (int64_t)blockIdx.x * rpw;
   const int64_t r_end = (r_beg + rpw < n) ? r_beg + rpw : n;
+  // f32 rows: x - K between two f32 values ROUNDS (2^-24 |x - K| a term), which a column whose mean is small beside its
+  // spread shows in save_mean (46 ulp on 31 rows, 512 on two: tests/test_batchnorm_edges_gpu.py).  The mean is therefore
+  // taken from a third sum of the differences in f64, where they are exact.  M2 stays the sum over the f32 differences
+  // about THEIR OWN mean (s2 - s1^2 / count): the exact M2 of values 2^-24 away from the data, inside invstd's bound,
+  // and the bits it always had.  Between two bf16 values the f32 difference is exact (unless the exponents lie 16
+  // binades apart) and nothing changes.
+  constexpr bool EXACT1 = sizeof(T) == 4;
   float shift[VEC];
-  double s1[VEC], s2[VEC];
+  double s1[VEC], s2[VEC], sx[VEC];
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) { shift[i] = 0.f; s1[i] = 0.; s2[i] = 0.; }
+  for (int i = 0; i < VEC; ++i) { shift[i] = 0.f; s1[i] = 0.; s2[i] = 0.; sx[i] = 0.; }
   if (rl < rpi) {
     IO<T>::unpack(*reinterpret_cast<const typename IO<T>::vec*>(x + r_beg * c + cg * VEC), shift);
     int64_t r = r_beg + rl;
@@ -131,14 +138,14 @@ __global__ void __launch_bounds__(NT) bn_stats_partial_kernel(const T* __restric
         float f[VEC];
         IO<T>::unpack(v[u], f);
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) { float d = f[i] - shift[i]; s1[i] += (double)d; s2[i] += (double)d * (double)d; }
+        for (int i = 0; i < VEC; ++i) { float d = f[i] - shift[i]; s1[i] += (double)d; s2[i] += (double)d * (double)d; if (EXACT1) sx[i] += (double)f[i] - (double)shift[i]; }
       }
     }
     for (; r < r_end; r += rpi) {
       float f[VEC];
       IO<T>::unpack(*reinterpret_cast<const typename IO<T>::vec*>(x + r * c + cg * VEC), f);
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) { float d = f[i] - shift[i]; s1[i] += (double)d; s2[i] += (double)d * (double)d; }
+      for (int i = 0; i < VEC; ++i) { float d = f[i] - shift[i]; s1[i] += (double)d; s2[i] += (double)d * (double)d; if (EXACT1) sx[i] += (double)f[i] - (double)shift[i]; }
     }
   }
   double* a1 = sh; double* a2 = sh + NT * VEC;
@@ -146,14 +153,23 @@ __global__ void __launch_bounds__(NT) bn_stats_partial_kernel(const T* __restric
   for (int i = 0; i < VEC; ++i) { a1[tid * VEC + i] = s1[i]; a2[tid * VEC + i] = s2[i]; }
   tree_sum_rows<VEC, double>(a1, tid, cg_n, rpi, rl);
   tree_sum_rows<VEC, double>(a2, tid, cg_n, rpi, rl);
+  double t1[VEC], t2[VEC], tx[VEC];
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) { t1[i] = a1[tid * VEC + i]; t2[i] = a2[tid * VEC + i]; tx[i] = t1[i]; }
+  if (EXACT1) {           // (a thread rewrites its own slot only, and every read of the first tree lies behind a barrier)
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) a1[tid * VEC + i] = sx[i];
+    tree_sum_rows<VEC, double>(a1, tid, cg_n, rpi, rl);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) tx[i] = a1[tid * VEC + i];
+  }
   if (rl == 0) {
     const double cnt = (double)(r_end - r_beg);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
-      double t1 = a1[tid * VEC + i], t2 = a2[tid * VEC + i];
-      double d = t1 / cnt, m2 = t2 - t1 * d;
+      double d = t1[i] / cnt, m2 = t2[i] - t1[i] * d;
       double* dst = part + ((int64_t)blockIdx.x * c + cg * VEC + i) * 3;
-      dst[0] = cnt; dst[1] = (double)shift[i] + d; dst[2] = m2 < 0. ? 0. : m2;
+      dst[0] = cnt; dst[1] = (double)shift[i] + (EXACT1 ? tx[i] / cnt : d); dst[2] = m2 < 0. ? 0. : m2;
     }
   }
 }

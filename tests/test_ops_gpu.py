@@ -1464,18 +1464,7 @@ def test_batchnorm_backward_slab_sums_against_the_f64_sums(n, c, ld, relu):
     assert float((err / (2.0 ** -7 * ref[0].double().abs().clamp_min(1e-3))).max()) <= 1.0 + 1e-6
 
 
-def _tile_triples(x, tile=128):
-    """(count, mean, M2) per 128-row tile and channel, what a convolution's epilogue leaves: f32, laid out
-    [c][tiles][3] (csrc/conv_img.hip store_tile) -- returned with that buffer's shape recorded as (tiles, c, 3)."""
-    n, c = x.shape
-    xf = x.float()
-    out = []
-    for r in range(0, n, tile):
-        blk = xf[r:r + tile]
-        m = blk.mean(0)
-        out.append(torch.stack([torch.full_like(m, blk.shape[0]), m, ((blk - m) ** 2).sum(0)], 1))
-    t = torch.stack(out, 0)                                     # [tiles, c, 3]
-    return t.permute(1, 0, 2).contiguous().view(t.shape[0], t.shape[1], 3)     # the bytes of [c][tiles][3]
+from batchnorm_ref import _tile_triples      # noqa: E402  (shared with test_batchnorm_edges_gpu.py)
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
