@@ -17,6 +17,7 @@
 // Everything else -- row order by occupancy pattern, per-tile offset masks, buffer addressing with
 // the hardware range check serving absent rules, scalar offset walk, copy-free two-set software
 // pipeline, epilogues -- is as described in conv.hip / DESIGN.md.
+#include <atomic>
 #include <type_traits>
 
 #include "common.h"
@@ -67,7 +68,7 @@ __host__ __device__ inline Tiling pick_tiling(int ci, int co, int64_t n_out, int
   t.row_bytes = (row_bytes % 192 == 0 && row_bytes % 128 != 0) ? 192
                 : (row_bytes % 128 != 0 && row_bytes % 64 == 0) ? 64 : 128;
   // (256-byte slices -- half the phases per offset on the layers of >= 128 channels -- measured no
-  // better, profiles/README.md; the 256-byte kernels stay instantiated for the image packer's sake)
+  // better, profiles/README.md; no kernel is instantiated for them -- the image packer takes its slice at run time)
   if (co <= 32) t.nb = 2;
   else if (co <= 64 || (co % 64 == 0 && ((n_out + 127) / 128) * ((co + 127) / 128) <= NB4_LIMIT)) t.nb = 4;
   else if (co % 128 != 0 && (co % 96 == 0 || co < 128)) t.nb = 6;
@@ -262,7 +263,25 @@ struct BnBwd {
 // statistics, BatchNorm backward sums) exactly as the unsplit kernel does.  Deterministic; differs from the unsplit
 // result only by the association of the f32 sum over the offsets.
 struct Split { float* partial; int nsplit; int co_pad; long long rows_pad; };
+constexpr Split NO_SPLIT{nullptr, 1, 0, 0};
 
+// The active offsets of a tile, as a wave-uniform mask in walk order (kflip: the data gradient walks the table's
+// offsets backwards): the OR of the 128-row masks the tile covers; the identity rule list of a per-row product
+// (DENSE: no table at all, K == 1) is offset 0.
+template <int BM, bool DENSE>
+__device__ __forceinline__ unsigned tile_mask(const unsigned* __restrict__ tmasks, int tile, int64_t n_out, int K, int kflip) {
+  if constexpr (DENSE) {
+    return 1u;
+  } else {
+    unsigned m = 0u;
+    const int64_t t0 = ((int64_t)tile * BM) >> 7;
+#pragma unroll
+    for (int h = 0; h < (BM >= 128 ? BM / 128 : 1); ++h)
+      if ((t0 + h) * 128 < n_out) m |= tmasks[t0 + h];
+    if (kflip) m = __brev(m) >> (32 - K);
+    return __builtin_amdgcn_readfirstlane(m);
+  }
+}
 // ---- epilogue shared by the kernels of this file (as conv.hip): accumulators (D layout: col =
 // lane&15, row = 4*(lane>>4) + r) -> wave-private LDS tile in T -> whole rows to HBM, 16-byte stores,
 // with the optional affine map / ReLU / residual of the inference paths
@@ -513,20 +532,7 @@ conv_apply_img_kernel(const T* __restrict__ in, const T* __restrict__ wimg,
   const int n0 = wg.col() * BN;
   const int npass = (ci + KC - 1) / KC;
 
-  // ---- tile mask: the OR of the 128-row masks this tile covers (scalar loads)
-  unsigned tmask;
-  if constexpr (DENSE) {          // no table at all: the identity rule list of a per-row product (K == 1)
-    tmask = 1u;
-  } else {
-    unsigned m = 0u;
-    const int64_t t0 = ((int64_t)bx * BM) >> 7;
-#pragma unroll
-    for (int h = 0; h < (BM >= 128 ? BM / 128 : 1); ++h)
-      if ((t0 + h) * 128 < n_out) m |= tmasks[t0 + h];
-    if (kflip) m = __brev(m) >> (32 - K);
-    tmask = m;
-  }
-  tmask = __builtin_amdgcn_readfirstlane(tmask);
+  const unsigned tmask = tile_mask<BM, DENSE>(tmasks, bx, n_out, K, kflip);
   const int n_act = __popc(tmask);
   const int nphase = n_act * npass;
 
@@ -747,6 +753,37 @@ __device__ unsigned long long* g_stamp_buf = nullptr;
 #define LIDAL_NOW() __builtin_readcyclecounter()
 #endif
 
+// ---- what the lean, deep and split kernels do alike and hipcc lets them share (with tile_mask above) ---------------
+// These are called from the kernels' own lambdas, with by-value scalars in the order the parent text first used them:
+// every kernel of this unit keeps its instruction stream.  A context STRUCT for the tile (decode, descriptors,
+// invariants, walk, index load, slab DMA as members), a shared two-set loop, a shared slab DMA and a shared
+// share-of-the-offsets loop were built and compiled too: each moved the instruction stream of every kernel that used it
+// (profiles/README.md, "The lean convolution kernels"), so those pieces stay as each kernel's own text.
+// The walk over (active offset, slice): one scalar state, advanced once per phase.
+__device__ __forceinline__ void walk_advance(int& wpass, int npass, int& wk, unsigned& rem) {
+  if (++wpass == npass) {
+    wpass = 0;
+    wk = rem ? __builtin_ctz(rem) : 0;              // past the end: offset 0 (a harmless index load)
+    rem &= rem - 1u;
+  }
+}
+// The neighbour index of this lane's row for offset k: requested a phase before the gather that uses it.
+// (a dense product has no table: the row is its own neighbour)
+__device__ __forceinline__ int nbr_index(int kflip, int K, int k, __amdgpu_buffer_rsrc_t rs_nbr, unsigned idx_voff,
+                                         unsigned k_stride) {
+  const unsigned kk = (unsigned)(kflip ? (K - 1 - k) : k);
+  return __builtin_amdgcn_raw_buffer_load_b32(rs_nbr, idx_voff, kk * k_stride, 0);
+}
+// A share of the tile's offsets (struct Split): the f32 accumulators go to conv_combine_kernel.
+template <int NB, int NWAVES, bool PAIRED>
+__device__ __forceinline__ void store_partial(const Split& sp, const WgTile<PAIRED>& wg, int wave, int lane,
+                                              const f32x4 (&acc)[1][NB]) {
+  f32x4* dst = reinterpret_cast<f32x4*>(sp.partial) +
+               ((((int64_t)blockIdx.z * wg.tiles() + wg.tile) * wg.ncol() + wg.col()) * NWAVES + wave) * (NB * 64) + lane;
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) dst[nb * 64] = acc[0][nb];
+}
+
 template <typename T, int NB, int ROW_BYTES, int NWAVES, bool DENSE, bool PAIRED>
 __global__ void __launch_bounds__(64 * NWAVES, (NWAVES == 8 ? LEAN_MINWAVES : 4))
 conv_lean_kernel(const T* __restrict__ in, const T* __restrict__ wimg, const int* __restrict__ nbr,
@@ -785,16 +822,9 @@ conv_lean_kernel(const T* __restrict__ in, const T* __restrict__ wimg, const int
   const int n0 = wg.col() * BN;
   const int npass = ci / KC;
 
-  unsigned tmask = 1u;
+  unsigned tmask = tile_mask<BM, DENSE>(tmasks, bx, n_out, K, kflip);
   if constexpr (!DENSE) {
-    unsigned m = 0u;
-    const int64_t t0 = ((int64_t)bx * BM) >> 7;
-#pragma unroll
-    for (int h = 0; h < (BM >= 128 ? BM / 128 : 1); ++h)
-      if ((t0 + h) * 128 < n_out) m |= tmasks[t0 + h];
-    if (kflip) m = __brev(m) >> (32 - K);
-    tmask = __builtin_amdgcn_readfirstlane(m);
-    if (sp.nsplit > 1) {        // this workgroup's share of the tile's active offsets: ranks [lo, hi) of the set bits
+    if (sp.nsplit > 1) {        // this workgroup's share of the tile's active offsets (struct Split): ranks [lo, hi) of the set bits
       const int cnt = __popc(tmask), z = (int)blockIdx.z;
       const int lo = z * cnt / sp.nsplit, hi = (z + 1) * cnt / sp.nsplit;
       unsigned left = tmask, sub = 0u;
@@ -839,20 +869,10 @@ conv_lean_kernel(const T* __restrict__ in, const T* __restrict__ wimg, const int
   // the walk over (active offset, slice): one scalar state, advanced once per phase
   unsigned rem = tmask;
   int wk = 0, wpass = npass - 1;
-  auto advance = [&]() {
-    if (++wpass == npass) {
-      wpass = 0;
-      wk = rem ? __builtin_ctz(rem) : 0;            // past the end: offset 0 (a harmless index load)
-      rem &= rem - 1u;
-    }
-  };
+  auto advance = [&]() { walk_advance(wpass, npass, wk, rem); };
   auto issue_idx = [&](int k) -> int {
-    if constexpr (DENSE) {
-      return (int)(r0 + row16);
-    } else {
-      const unsigned kk = (unsigned)(kflip ? (K - 1 - k) : k);
-      return __builtin_amdgcn_raw_buffer_load_b32(rs_nbr, idx_voff, kk * k_stride, 0);
-    }
+    if constexpr (DENSE) return (int)(r0 + row16);
+    else return nbr_index(kflip, K, k, rs_nbr, idx_voff, k_stride);
   };
   // EVERY wave issues PPW DMA instructions per phase -- a wave without a share of the slab aims out of range
   // (zeros, no memory traffic) at the dump: hipcc counts vector-memory operations statically, and behind a
@@ -983,13 +1003,7 @@ conv_lean_kernel(const T* __restrict__ in, const T* __restrict__ wimg, const int
 #undef ST_ISSUED
 #undef ST_COMPUTED
 #undef ST_PHASE_END
-  if (sp.nsplit > 1) {          // a share of the tile's offsets: the f32 accumulators go to the combining kernel
-    f32x4* dst = reinterpret_cast<f32x4*>(sp.partial) +
-                 ((((int64_t)blockIdx.z * wg.tiles() + bx) * wg.ncol() + wg.col()) * NWAVES + wave) * (NB * 64) + lane;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) dst[nb * 64] = acc[0][nb];
-    return;
-  }
+  if (sp.nsplit > 1) { store_partial<NB, NWAVES>(sp, wg, wave, lane, acc); return; }
   store_tile<T, NB, 1, NWAVES>(acc, wl, wave, lane, r0, n0, n_out, co, perm, out, ep_scale, ep_shift, ep_relu,
                                ep_res, true, perm_v, tile_stats, bx, &bnb, wg.stats_tiles());
 #ifdef LIDAL_PHASE_STAMPS
@@ -1095,14 +1109,7 @@ conv_lean_deep_kernel(const T* __restrict__ in, const T* __restrict__ wimg, cons
   const int n0 = wg.col() * BN;
   const int npass = ci / KC;
 
-  unsigned tmask = 1u;
-  if constexpr (!DENSE) {
-    unsigned m = 0u;
-    const int64_t t0 = ((int64_t)bx * BM) >> 7;
-    if (t0 * 128 < n_out) m = tmasks[t0];
-    if (kflip) m = __brev(m) >> (32 - K);
-    tmask = __builtin_amdgcn_readfirstlane(m);
-  }
+  const unsigned tmask = tile_mask<BM, DENSE>(tmasks, bx, n_out, K, kflip);
   const int nphase = __popc(tmask) * npass;
 
   const __amdgpu_buffer_rsrc_t rs_in =
@@ -1131,20 +1138,10 @@ conv_lean_deep_kernel(const T* __restrict__ in, const T* __restrict__ wimg, cons
 
   unsigned rem = tmask;
   int wk = 0, wpass = npass - 1;
-  auto advance = [&]() {
-    if (++wpass == npass) {
-      wpass = 0;
-      wk = rem ? __builtin_ctz(rem) : 0;
-      rem &= rem - 1u;
-    }
-  };
+  auto advance = [&]() { walk_advance(wpass, npass, wk, rem); };
   auto issue_idx = [&](int k) -> int {
-    if constexpr (DENSE) {
-      return (int)(r0 + row16);
-    } else {
-      const unsigned kk = (unsigned)(kflip ? (K - 1 - k) : k);
-      return __builtin_amdgcn_raw_buffer_load_b32(rs_nbr, idx_voff, kk * k_stride, 0);
-    }
+    if constexpr (DENSE) return (int)(r0 + row16);
+    else return nbr_index(kflip, K, k, rs_nbr, idx_voff, k_stride);
   };
   // every DMA wave issues its PPW pieces in EVERY phase (a phase past the end reads out of range -- zeros,
   // no memory traffic -- into the dump): the counted waits below rely on it
@@ -1336,13 +1333,8 @@ conv_split_kernel(const float* __restrict__ in, const __bf16* __restrict__ wimg,
   const int n0 = wg.col() * BN;
   const int npass = ci / SPLIT_KCH;
 
-  unsigned tmask = 1u;
+  unsigned tmask = tile_mask<BM, DENSE>(tmasks, bx, n_out, K, kflip);
   if constexpr (!DENSE) {
-    unsigned m = 0u;
-    const int64_t t0 = ((int64_t)bx * BM) >> 7;
-    if (t0 * 128 < n_out) m = tmasks[t0];
-    if (kflip) m = __brev(m) >> (32 - K);
-    tmask = __builtin_amdgcn_readfirstlane(m);
     if (sp.nsplit > 1) {        // this workgroup's share of the tile's active offsets (struct Split): ranks [lo, hi) of the set bits
       const int cnt = __popc(tmask), z = (int)blockIdx.z;
       const int lo = z * cnt / sp.nsplit, hi = (z + 1) * cnt / sp.nsplit;
@@ -1383,20 +1375,10 @@ conv_split_kernel(const float* __restrict__ in, const __bf16* __restrict__ wimg,
 
   unsigned rem = tmask;
   int wk = 0, wpass = npass - 1;
-  auto advance = [&]() {
-    if (++wpass == npass) {
-      wpass = 0;
-      wk = rem ? __builtin_ctz(rem) : 0;
-      rem &= rem - 1u;
-    }
-  };
+  auto advance = [&]() { walk_advance(wpass, npass, wk, rem); };
   auto issue_idx = [&](int k) -> int {
-    if constexpr (DENSE) {
-      return (int)(r0 + row16);
-    } else {
-      const unsigned kk = (unsigned)(kflip ? (K - 1 - k) : k);
-      return __builtin_amdgcn_raw_buffer_load_b32(rs_nbr, idx_voff, kk * k_stride, 0);
-    }
+    if constexpr (DENSE) return (int)(r0 + row16);
+    else return nbr_index(kflip, K, k, rs_nbr, idx_voff, k_stride);
   };
   auto issue_dma = [&](int k, int pass, auto slot_c) {
     constexpr int slot = decltype(slot_c)::value;
@@ -1494,13 +1476,7 @@ conv_split_kernel(const float* __restrict__ in, const __bf16* __restrict__ wimg,
     }
     __syncthreads();
   }
-  if (sp.nsplit > 1) {          // a share of the tile's offsets: the f32 accumulators go to conv_combine_kernel
-    f32x4* dst = reinterpret_cast<f32x4*>(sp.partial) +
-                 ((((int64_t)blockIdx.z * wg.tiles() + bx) * wg.ncol() + wg.col()) * NWAVES + wave) * (NB * 64) + lane;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) dst[nb * 64] = acc[0][nb];
-    return;
-  }
+  if (sp.nsplit > 1) { store_partial<NB, NWAVES>(sp, wg, wave, lane, acc); return; }
   store_tile<float, NB, 1, NWAVES>(acc, wl, wave, lane, r0, n0, n_out, co, perm, out, ep_scale, ep_shift, ep_relu,
                                    ep_res, true, perm_v, nullptr, bx, nullptr);
 }
@@ -1576,10 +1552,50 @@ constexpr int64_t SPLIT_MAX_WGS = 256;
 // 265 -> 183-185 us with the offsets split three ways; at stride 8 (1038-1350 workgroups) neutral to -4 %, at stride 4
 // (1265 workgroups) 136 -> 185 us: a loss -- the f32 partial tiles cost more than the tail they remove
 constexpr int64_t SPLIT_F32_MAX_WGS = 512;
-__host__ inline int pick_split(int64_t wgs, int K, int npass) {
-  if (wgs > SPLIT_MAX_WGS || K * npass < 27) return 1;
-  return wgs <= 128 ? 4 : (wgs <= 192 ? 3 : 2);
+constexpr int SPLIT_MAX_SHARES = 4;
+constexpr int64_t SPLIT_ANY_MAX_WGS = SPLIT_F32_MAX_WGS > SPLIT_MAX_WGS ? SPLIT_F32_MAX_WGS : SPLIT_MAX_WGS;
+// The Split of a launch of tiles x ny workgroups (bm rows x bn columns each), K offsets of npass slices: how many
+// shares (f32_form: conv_split_kernel's rule, else the bf16 lean kernel's), and none unless the workspace holds them.
+// A tile of a coarse level runs up to 27 offsets x Cin/32 slices back to back (216 phases of ~1 us at 256 channels in
+// the f32 form) while the launch has one to two rounds of workgroups -- as long as its heaviest tile and a quantised
+// round count.  lidal_conv_apply_workspace_bytes sizes the workspace from the same constants.
+__host__ inline Split split_plan(int64_t tiles, int64_t ny, int K, int npass, bool f32_form, int bm, int bn, void* ws,
+                                 long long ws_bytes) {
+  const int64_t wgs = tiles * ny;
+  const int ns = f32_form ? ((wgs > SPLIT_F32_MAX_WGS || K * npass < 54) ? 1 : (wgs <= 256 ? 4 : 3))
+                          : ((wgs > SPLIT_MAX_WGS || K * npass < 27) ? 1 : (wgs <= 128 ? 4 : (wgs <= 192 ? 3 : 2)));
+  static_assert(SPLIT_MAX_SHARES == 4, "the largest share count above");
+  const long long rows_pad = (long long)tiles * bm;
+  const int co_pad = (int)ny * bn;
+  if (ws == nullptr || ns <= 1 || ws_bytes < (long long)ns * rows_pad * co_pad * 4) return NO_SPLIT;
+  return Split{(float*)ws, ns, co_pad, rows_pad};
 }
+
+// Launch `kernel` with lds_bytes of dynamic LDS.  hipFuncAttributeMaxDynamicSharedMemorySize is set once per (kernel,
+// device) to at least that and remembered in a table of this instantiation: one per launcher (`Site`) and kernel
+// signature, which the launcher's ternaries fill with at most four kernels (DENSE x PAIRED).  A slot is claimed
+// atomically; two threads that race on one kernel's entry at worst both set the attribute, as before.
+template <class Site, typename... P, typename... A>
+int launch_lds(void (*kernel)(P...), dim3 grid, unsigned threads, size_t lds_bytes, hipStream_t s, const char* what,
+               A... args) {
+  static std::atomic<const void*> known[4] = {};
+  static size_t set[4][MAX_DEVICES] = {};
+  const void* const fn = reinterpret_cast<const void*>(kernel);
+  int i = 0;
+  for (; i < 4; ++i) {              // this kernel's slot, or the first free one
+    const void* seen = nullptr;
+    if (known[i].load() == fn || known[i].compare_exchange_strong(seen, fn) || seen == fn) break;
+  }
+  const int dev = current_device();
+  if (i == 4 || set[i][dev] < lds_bytes) {          // (a fifth kernel would set the attribute at every launch)
+    LIDAL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    if (i < 4) set[i][dev] = lds_bytes;
+  }
+  kernel<<<grid, threads, lds_bytes, s>>>(static_cast<P>(args)...);
+  LIDAL_CHECK_LAUNCH(what);
+  return 0;
+}
+constexpr BnBwd NO_BNB{};
 
 constexpr int IMG_G = 1, IMG_NWAVES = 8, IMG_DEPTH = 1;       // generic kernel: row groups per wave, waves, pipeline depth
 
@@ -1608,6 +1624,7 @@ int launch_img(const void* in, const void* wimg, const int* nbr, const int* perm
   constexpr int WREGION = ((D + 1) * SLAB > EPI) ? (D + 1) * SLAB : EPI;
   static_assert(BM == TILE_ROWS, "tile masks and BatchNorm statistics triples are per 128-row tile");
   constexpr bool CAN_PAIR = NB > 2;
+  struct Here {};                   // launch_lds: the kernels of this tiling
   const unsigned tiles = (unsigned)cdiv(n_out, BM), ny = (unsigned)cdiv(co, BN);
   const bool paired = CAN_PAIR && pair_columns(ny, n_out);
   if constexpr (G == 1 && NWAVES == 8) {
@@ -1632,63 +1649,33 @@ int launch_img(const void* in, const void* wimg, const int* nbr, const int* perm
         constexpr int DEEP_LDS = ((3 * SLAB > DEPI) ? 3 * SLAB : DEPI) + 4096;
         auto dk = paired ? conv_lean_deep_kernel<T, NB, ROW_BYTES, LW, false, CAN_PAIR>
                          : conv_lean_deep_kernel<T, NB, ROW_BYTES, LW, false, false>;
-        static size_t deep_attr[2][MAX_DEVICES] = {};
-        const int ddev = current_device();
-        if (deep_attr[paired][ddev] < (size_t)DEEP_LDS) {
-          LIDAL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dk),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, DEEP_LDS));
-          deep_attr[paired][ddev] = DEEP_LDS;
-        }
-        const dim3 dgrid = conv_grid(paired, tiles, ny);
-        dk<<<dgrid, 64 * LW, DEEP_LDS, s>>>((const T*)in, (const T*)wimg, nbr, perm, tmasks, (T*)out, n_out,
-                                            ci, co, K, kflip, ep.scale, ep.shift, ep.relu, (const T*)ep.res,
-                                            ep.in_bytes, ep.img_bytes, ep.nbr_bytes, ep.tile_stats, ep.bnb);
-        LIDAL_CHECK_LAUNCH("lidal_conv_apply_image(deep)");
-        return 0;
+        return launch_lds<Here>(dk, conv_grid(paired, tiles, ny), 64 * LW, DEEP_LDS, s, "lidal_conv_apply_image(deep)",
+                                (const T*)in, (const T*)wimg, nbr, perm, tmasks, (T*)out, n_out, ci, co, K, kflip, ep.scale,
+                                ep.shift, ep.relu, (const T*)ep.res, ep.in_bytes, ep.img_bytes, ep.nbr_bytes, ep.tile_stats,
+                                ep.bnb);
        }
       }
       auto lk = paired ? (nbr ? conv_lean_kernel<T, NB, ROW_BYTES, LW, false, CAN_PAIR>
                               : conv_lean_kernel<T, NB, ROW_BYTES, LW, true, CAN_PAIR>)
                        : (nbr ? conv_lean_kernel<T, NB, ROW_BYTES, LW, false, false>
                               : conv_lean_kernel<T, NB, ROW_BYTES, LW, true, false>);
-      static size_t lean_attr[4][MAX_DEVICES] = {};
-      const int ldev = current_device(), lsel = (nbr ? 0 : 1) + (paired ? 2 : 0);
-      if (lean_attr[lsel][ldev] < (size_t)LEAN_LDS) {
-        LIDAL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lk),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, LEAN_LDS));
-        lean_attr[lsel][ldev] = LEAN_LDS;
-      }
-      dim3 lgrid(tiles, ny);                 // the combining kernel's grid; the lean kernel's is conv_grid()
-      Split sp{nullptr, 1, 0, 0};
       // (bf16 only: the f32 parity mode keeps ONE f32 sum over the offsets per output element, the association its
       // golden gradients were taken with -- through 49 train-mode BatchNorm layers a last-bit change of a sum moves
       // end-to-end gradients by up to 1e-3)
-      if (nbr != nullptr && ep.ws != nullptr && sizeof(T) == 2) {
-        const int ns = pick_split((int64_t)lgrid.x * lgrid.y, K, ci / (ROW_BYTES / (int)sizeof(T)));
-        const long long rows_pad = (long long)lgrid.x * LBM;
-        const int co_pad = (int)lgrid.y * BN;
-        if (ns > 1 && ep.ws_bytes >= (long long)ns * rows_pad * co_pad * 4)
-          sp = Split{(float*)ep.ws, ns, co_pad, rows_pad};
-      }
+      const Split sp = (nbr != nullptr && sizeof(T) == 2)
+                           ? split_plan(tiles, ny, K, ci / (ROW_BYTES / (int)sizeof(T)), false, LBM, BN, ep.ws, ep.ws_bytes)
+                           : NO_SPLIT;
       dim3 kgrid = conv_grid(paired, tiles, ny);
       kgrid.z = (unsigned)sp.nsplit;
-      lk<<<kgrid, 64 * LW, LEAN_LDS, s>>>((const T*)in, (const T*)wimg, nbr, perm, tmasks, (T*)out, n_out,
-                                          ci, co, K, kflip, ep.scale, ep.shift, ep.relu, (const T*)ep.res,
-                                          ep.in_bytes, ep.img_bytes, ep.nbr_bytes, ep.tile_stats, ep.bnb, sp);
-      LIDAL_CHECK_LAUNCH("lidal_conv_apply_image(lean)");
-      if (sp.nsplit > 1) {
-        constexpr int COMB_LDS = LEPI + LSTATS;
-        auto ck = conv_combine_kernel<T, NB, LW>;
-        static size_t comb_attr[MAX_DEVICES] = {};
-        if (comb_attr[ldev] < (size_t)COMB_LDS) {
-          LIDAL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ck),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, COMB_LDS));
-          comb_attr[ldev] = COMB_LDS;
-        }
-        ck<<<lgrid, 64 * LW, COMB_LDS, s>>>(sp, perm, (T*)out, n_out, co, ep.scale, ep.shift, ep.relu,
-                                            (const T*)ep.res, ep.tile_stats, ep.bnb);
-        LIDAL_CHECK_LAUNCH("lidal_conv_apply_image(combine)");
-      }
+      if (int rc = launch_lds<Here>(lk, kgrid, 64 * LW, LEAN_LDS, s, "lidal_conv_apply_image(lean)", (const T*)in,
+                                    (const T*)wimg, nbr, perm, tmasks, (T*)out, n_out, ci, co, K, kflip, ep.scale, ep.shift,
+                                    ep.relu, (const T*)ep.res, ep.in_bytes, ep.img_bytes, ep.nbr_bytes, ep.tile_stats, ep.bnb,
+                                    sp))
+        return rc;
+      if (sp.nsplit > 1)          // its own grid (tile, column block), whatever grid the lean kernel ran on
+        return launch_lds<Here>(conv_combine_kernel<T, NB, LW>, dim3(tiles, ny), 64 * LW, LEPI + LSTATS, s,
+                                "lidal_conv_apply_image(combine)", sp, perm, (T*)out, n_out, co, ep.scale, ep.shift,
+                                ep.relu, (const T*)ep.res, ep.tile_stats, ep.bnb);
       return 0;
     }
   }
@@ -1697,19 +1684,9 @@ int launch_img(const void* in, const void* wimg, const int* nbr, const int* perm
                             : conv_apply_img_kernel<T, NB, ROW_BYTES, G, NWAVES, IMG_MINWAVES, true, D, CAN_PAIR>)
                      : (nbr ? conv_apply_img_kernel<T, NB, ROW_BYTES, G, NWAVES, IMG_MINWAVES, false, D, false>
                             : conv_apply_img_kernel<T, NB, ROW_BYTES, G, NWAVES, IMG_MINWAVES, true, D, false>);
-  static size_t attr_set[4][MAX_DEVICES] = {};
-  const int dev = current_device(), sel = (nbr ? 0 : 1) + (paired ? 2 : 0);
-  if (attr_set[sel][dev] < lds) {
-    LIDAL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set[sel][dev] = lds;
-  }
-  const dim3 grid = conv_grid(paired, tiles, ny);
-  kern<<<grid, NTHREADS, lds, s>>>((const T*)in, (const T*)wimg, nbr, perm, tmasks, (T*)out, n_out, ci,
-                                   co, K, kflip, ep.scale, ep.shift, ep.relu, (const T*)ep.res,
-                                   ep.in_bytes, ep.img_bytes, ep.nbr_bytes, ep.tile_stats, ep.bnb);
-  LIDAL_CHECK_LAUNCH("lidal_conv_apply_image");
-  return 0;
+  return launch_lds<Here>(kern, conv_grid(paired, tiles, ny), NTHREADS, lds, s, "lidal_conv_apply_image", (const T*)in,
+                          (const T*)wimg, nbr, perm, tmasks, (T*)out, n_out, ci, co, K, kflip, ep.scale, ep.shift, ep.relu,
+                          (const T*)ep.res, ep.in_bytes, ep.img_bytes, ep.nbr_bytes, ep.tile_stats, ep.bnb);
 }
 
 template <typename T>
@@ -1722,7 +1699,6 @@ int dispatch_img(Tiling t, const void* in, const void* wimg, const int* nbr, con
   IMG_CASE(2, 64) IMG_CASE(4, 64) IMG_CASE(6, 64) IMG_CASE(8, 64)
   IMG_CASE(2, 128) IMG_CASE(4, 128) IMG_CASE(6, 128) IMG_CASE(8, 128)
   IMG_CASE(2, 192) IMG_CASE(4, 192) IMG_CASE(6, 192) IMG_CASE(8, 192)
-  IMG_CASE(2, 256) IMG_CASE(4, 256) IMG_CASE(6, 256) IMG_CASE(8, 256)
 #undef IMG_CASE
   set_error("conv_apply_image: no kernel for tiling nb=%d row_bytes=%d", t.nb, t.row_bytes);
   return 2;
@@ -1742,42 +1718,21 @@ int launch_split(const void* in, const void* wimg, const int* nbr, const int* pe
   constexpr int LEPI_ALL = LW * 16 * (BN + 4) * 4 + LW * BN * 2 * (int)sizeof(float);
   constexpr int LDS = ((2 * SLAB > LEPI_ALL) ? 2 * SLAB : LEPI_ALL) + 4096;
   auto kern = nbr ? conv_split_kernel<NB, LW, false> : conv_split_kernel<NB, LW, true>;
-  static size_t attr[2][MAX_DEVICES] = {};
-  const int dev = current_device();
-  if (attr[nbr ? 0 : 1][dev] < (size_t)LDS) {
-    LIDAL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr[nbr ? 0 : 1][dev] = LDS;
-  }
+  struct Here {};                   // launch_lds: the kernels of this block width
   dim3 grid((unsigned)cdiv(n_out, LW * 16), (unsigned)cdiv(co, BN));
-  // The offsets of a tile over several workgroups (struct Split) where the launch does not fill the chip once: a
-  // tile of a coarse level runs up to 27 offsets x Cin/32 slices back to back (216 phases of ~1 us at 256 channels)
-  // while the launch has one to two rounds of workgroups -- as long as its heaviest tile and a quantised round count.
-  Split sp{nullptr, 1, 0, 0};
-  if (nbr != nullptr && ep.ws != nullptr) {
-    const int64_t wgs = (int64_t)grid.x * grid.y;
-    const int ns = (wgs > SPLIT_F32_MAX_WGS || K * (ci / SPLIT_KCH) < 54) ? 1 : (wgs <= 256 ? 4 : 3);
-    const long long rows_pad = (long long)grid.x * LW * 16;
-    const int co_pad = (int)grid.y * BN;
-    if (ns > 1 && ep.ws_bytes >= (long long)ns * rows_pad * co_pad * 4) sp = Split{(float*)ep.ws, ns, co_pad, rows_pad};
-  }
+  // the offsets of a tile over several workgroups (struct Split) where the launch does not fill the chip once
+  const Split sp = nbr != nullptr ? split_plan(grid.x, grid.y, K, ci / SPLIT_KCH, true, LW * 16, BN, ep.ws, ep.ws_bytes)
+                                  : NO_SPLIT;
   grid.z = (unsigned)sp.nsplit;
-  kern<<<grid, 64 * LW, LDS, s>>>((const float*)in, (const __bf16*)wimg, nbr, perm, tmasks, (float*)out, n_out, ci, co, K,
-                                  kflip, ep.scale, ep.shift, ep.relu, (const float*)ep.res, ep.in_bytes, ep.img_bytes,
-                                  ep.nbr_bytes, sp);
-  LIDAL_CHECK_LAUNCH("lidal_conv_apply_image(split)");
+  if (int rc = launch_lds<Here>(kern, grid, 64 * LW, LDS, s, "lidal_conv_apply_image(split)", (const float*)in,
+                                (const __bf16*)wimg, nbr, perm, tmasks, (float*)out, n_out, ci, co, K, kflip, ep.scale,
+                                ep.shift, ep.relu, (const float*)ep.res, ep.in_bytes, ep.img_bytes, ep.nbr_bytes, sp))
+    return rc;
   if (sp.nsplit > 1) {
-    constexpr int COMB_LDS = LEPI_ALL;
-    auto ck = conv_combine_kernel<float, NB, LW>;
-    static size_t comb_attr[MAX_DEVICES] = {};
-    if (comb_attr[dev] < (size_t)COMB_LDS) {
-      LIDAL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ck), hipFuncAttributeMaxDynamicSharedMemorySize, COMB_LDS));
-      comb_attr[dev] = COMB_LDS;
-    }
     grid.z = 1;
-    BnBwd none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    ck<<<grid, 64 * LW, COMB_LDS, s>>>(sp, perm, (float*)out, n_out, co, ep.scale, ep.shift, ep.relu, (const float*)ep.res,
-                                       nullptr, none);
-    LIDAL_CHECK_LAUNCH("lidal_conv_apply_image(split, combine)");
+    return launch_lds<Here>(conv_combine_kernel<float, NB, LW>, grid, 64 * LW, LEPI_ALL, s,
+                            "lidal_conv_apply_image(split, combine)", sp, perm, (float*)out, n_out, co, ep.scale, ep.shift,
+                            ep.relu, (const float*)ep.res, (float*)nullptr, NO_BNB);
   }
   return 0;
 }
@@ -1798,49 +1753,60 @@ extern "C" int64_t lidal_conv_weight_image_bytes(int k, int ci, int co, int dtyp
   return image_bytes(k, ci, co, pick_tiling(ci, co, n_out, esz), esz);
 }
 
+// The image that reduces over n_red for launches of n_out rows: its tiling as the packer takes it (16-column blocks,
+// channels per slice; the split form has no slice argument: kc == 0) and its count of 16-byte segments
+struct ImgTiling { int nb, kc; };
+static ImgTiling image_tiling(int dtype, int n_red, int n_col, int64_t n_out) {
+  if (dtype == LIDAL_F32_SPLIT) return ImgTiling{split_nb(n_col), 0};
+  const int esz = dtype == LIDAL_BF16 ? 2 : 4;
+  const Tiling t = pick_tiling(n_red, n_col, n_out, esz);
+  return ImgTiling{t.nb, t.row_bytes / esz};
+}
+static int64_t image_segments(int dtype, int k, int n_red, int n_col, int64_t n_out) {
+  if (dtype == LIDAL_F32_SPLIT) return split_image_bytes(k, n_red, n_col) / 16;
+  const int esz = dtype == LIDAL_BF16 ? 2 : 4;
+  return image_bytes(k, n_red, n_col, pick_tiling(n_red, n_col, n_out, esz), esz) / 16;
+}
+// f((TI*)0, (TO*)0) for the element types of (weight dtype, image dtype); false: no such pair
+template <class F>
+static bool with_image_types(int w_dtype, int dtype, F&& f) {
+  if (w_dtype == LIDAL_F32 && dtype == LIDAL_F32) f((float*)nullptr, (float*)nullptr);
+  else if (w_dtype == LIDAL_F32 && dtype == LIDAL_BF16) f((float*)nullptr, (__bf16*)nullptr);
+  else if (w_dtype == LIDAL_BF16 && dtype == LIDAL_BF16) f((__bf16*)nullptr, (__bf16*)nullptr);
+  else if (w_dtype == LIDAL_BF16 && dtype == LIDAL_F32) f((__bf16*)nullptr, (float*)nullptr);
+  else return false;
+  return true;
+}
+
 static int weight_images(const void* w, int w_dtype, int role, void* img_a, int64_t n_out_a, void* img_b,
                          int64_t n_out_b, int dtype, int k, int n_red, int n_col, hipStream_t s) {
   if (k == 0 || n_red == 0 || n_col == 0) return 0;
   LIDAL_REQUIRE(role == 0 || role == 1, "weight_image: role must be 0 (forward) or 1 (data gradient)");
+  LIDAL_REQUIRE(dtype != LIDAL_F32_SPLIT || (img_b == nullptr && n_red % SPLIT_KCH == 0), "weight_image(split): one image "
+                "per call, reduction a multiple of %d channels (got %d)", SPLIT_KCH, n_red);
+  const ImgTiling ta = image_tiling(dtype, n_red, n_col, n_out_a);
+  const int64_t segs_a = image_segments(dtype, k, n_red, n_col, n_out_a);
   if (dtype == LIDAL_F32_SPLIT) {       // hi | mid | lo bf16 pieces of an f32 (or bf16) weight, see conv_split_kernel
-    LIDAL_REQUIRE(img_b == nullptr && n_red % SPLIT_KCH == 0, "weight_image(split): one image per call, reduction a "
-                  "multiple of %d channels (got %d)", SPLIT_KCH, n_red);
-    const int64_t segs = split_image_bytes(k, n_red, n_col) / 16;
-    LIDAL_REQUIRE(segs < (1ll << 31), "weight_image: an image of more than 2^31 segments");
-    const unsigned grid = (unsigned)cdiv(segs, 256);
+    LIDAL_REQUIRE(segs_a < (1ll << 31), "weight_image: an image of more than 2^31 segments");
+    const unsigned grid = (unsigned)cdiv(segs_a, 256);
     if (w_dtype == LIDAL_F32)
-      weight_image_split_kernel<float><<<grid, 256, 0, s>>>((const float*)w, (__bf16*)img_a, n_red, n_col, role,
-                                                            split_nb(n_col), segs);
+      weight_image_split_kernel<float><<<grid, 256, 0, s>>>((const float*)w, (__bf16*)img_a, n_red, n_col, role, ta.nb, segs_a);
     else
-      weight_image_split_kernel<__bf16><<<grid, 256, 0, s>>>((const __bf16*)w, (__bf16*)img_a, n_red, n_col, role,
-                                                             split_nb(n_col), segs);
+      weight_image_split_kernel<__bf16><<<grid, 256, 0, s>>>((const __bf16*)w, (__bf16*)img_a, n_red, n_col, role, ta.nb, segs_a);
     LIDAL_CHECK_LAUNCH("lidal_conv_weight_image(split)");
     return 0;
   }
-  const int esz = dtype == LIDAL_BF16 ? 2 : 4;
-  const Tiling ta = pick_tiling(n_red, n_col, n_out_a, esz);
-  const int64_t segs_a = image_bytes(k, n_red, n_col, ta, esz) / 16;
-  Tiling tb = ta;
-  int64_t segs_b = 0;
-  if (img_b != nullptr) {
-    tb = pick_tiling(n_col, n_red, n_out_b, esz);
-    segs_b = image_bytes(k, n_col, n_red, tb, esz) / 16;
-  }
+  const ImgTiling tb = img_b != nullptr ? image_tiling(dtype, n_col, n_red, n_out_b) : ta;
+  const int64_t segs_b = img_b != nullptr ? image_segments(dtype, k, n_col, n_red, n_out_b) : 0;
   LIDAL_REQUIRE(segs_a < (1ll << 31) && segs_b < (1ll << 31), "weight_image: an image of more than 2^31 segments");
   const unsigned grid = (unsigned)cdiv(segs_a + segs_b, 256);
-#define IMG_LAUNCH(TI, TO) \
-  weight_image_kernel<TI, TO><<<grid, 256, 0, s>>>((const TI*)w, (TO*)img_a, n_red, n_col, role, ta.nb, \
-                                                   ta.row_bytes / esz, segs_a, (TO*)img_b, tb.nb,       \
-                                                   tb.row_bytes / esz, segs_b)
-  if (w_dtype == LIDAL_F32 && dtype == LIDAL_F32) IMG_LAUNCH(float, float);
-  else if (w_dtype == LIDAL_F32 && dtype == LIDAL_BF16) IMG_LAUNCH(float, __bf16);
-  else if (w_dtype == LIDAL_BF16 && dtype == LIDAL_BF16) IMG_LAUNCH(__bf16, __bf16);
-  else if (w_dtype == LIDAL_BF16 && dtype == LIDAL_F32) IMG_LAUNCH(__bf16, float);
-  else {
-    set_error("weight_image: bad dtypes %d %d", w_dtype, dtype);
-    return 2;
-  }
-#undef IMG_LAUNCH
+  const bool known = with_image_types(w_dtype, dtype, [&](auto* ti, auto* to) {
+    using TI = std::remove_pointer_t<decltype(ti)>;
+    using TO = std::remove_pointer_t<decltype(to)>;
+    weight_image_kernel<TI, TO><<<grid, 256, 0, s>>>((const TI*)w, (TO*)img_a, n_red, n_col, role, ta.nb, ta.kc, segs_a,
+                                                     (TO*)img_b, tb.nb, tb.kc, segs_b);
+  });
+  LIDAL_REQUIRE(known, "weight_image: bad dtypes %d %d", w_dtype, dtype);
   LIDAL_CHECK_LAUNCH("lidal_conv_weight_image");
   return 0;
 }
@@ -1869,36 +1835,21 @@ extern "C" int64_t lidal_conv_weight_image_job(void* job, const void* w, int rol
     set_error("weight_image_job: bad arguments");
     return -1;
   }
-  if (dtype == LIDAL_F32_SPLIT) {       // reduction over ci; with img_bwd (training) also the image that reduces over co
-    if (ci % SPLIT_KCH != 0 || (img_bwd != nullptr && co % SPLIT_KCH != 0)) {
-      set_error("weight_image_job(split): the reduction must be a multiple of %d channels (got ci=%d%s co=%d)", SPLIT_KCH, ci,
-                img_bwd != nullptr ? ", data-gradient image:" : ",", co);
-      return -1;
-    }
-    ImageJob j;
-    j.w = w; j.img_a = img_fwd; j.img_b = img_bwd; j.first = first;
-    j.segs_a = split_image_bytes(k, ci, co) / 16;
-    j.segs_b = img_bwd != nullptr ? split_image_bytes(k, co, ci) / 16 : 0;
-    j.n_red = ci; j.n_col = co; j.role = role; j.nb_a = split_nb(co); j.kc_a = 0; j.nb_b = split_nb(ci); j.kc_b = 0; j.pad = 0;
-    if (j.segs_a >= (1ll << 31) || j.segs_b >= (1ll << 31)) {
-      set_error("weight_image_job: an image of %lld segments", (long long)(j.segs_a > j.segs_b ? j.segs_a : j.segs_b));
-      return -1;
-    }
-    *reinterpret_cast<ImageJob*>(job) = j;
-    return j.segs_a + j.segs_b;
+  const bool split = dtype == LIDAL_F32_SPLIT, both = img_bwd != nullptr;
+  // (split: reduction over ci; with img_bwd (training) also the image that reduces over co)
+  if (split && (ci % SPLIT_KCH != 0 || (both && co % SPLIT_KCH != 0))) {
+    set_error("weight_image_job(split): the reduction must be a multiple of %d channels (got ci=%d%s co=%d)", SPLIT_KCH, ci,
+              both ? ", data-gradient image:" : ",", co);
+    return -1;
   }
-  const int esz = dtype == LIDAL_BF16 ? 2 : 4;
-  const Tiling ta = pick_tiling(ci, co, n_out_fwd, esz);
+  const ImgTiling ta = image_tiling(dtype, ci, co, n_out_fwd);
+  // (without a second image its fields repeat the first one's -- in the split form they name its blocks all the same)
+  const ImgTiling tb = (both || split) ? image_tiling(dtype, co, ci, n_out_bwd) : ta;
   ImageJob j;
   j.w = w; j.img_a = img_fwd; j.img_b = img_bwd; j.first = first;
-  j.segs_a = image_bytes(k, ci, co, ta, esz) / 16;
-  j.n_red = ci; j.n_col = co; j.role = role; j.nb_a = ta.nb; j.kc_a = ta.row_bytes / esz;
-  j.segs_b = 0; j.nb_b = ta.nb; j.kc_b = j.kc_a; j.pad = 0;
-  if (img_bwd != nullptr) {
-    const Tiling tb = pick_tiling(co, ci, n_out_bwd, esz);
-    j.segs_b = image_bytes(k, co, ci, tb, esz) / 16;
-    j.nb_b = tb.nb; j.kc_b = tb.row_bytes / esz;
-  }
+  j.segs_a = image_segments(dtype, k, ci, co, n_out_fwd);
+  j.segs_b = both ? image_segments(dtype, k, co, ci, n_out_bwd) : 0;
+  j.n_red = ci; j.n_col = co; j.role = role; j.nb_a = ta.nb; j.kc_a = ta.kc; j.nb_b = tb.nb; j.kc_b = tb.kc; j.pad = 0;
   if (j.segs_a >= (1ll << 31) || j.segs_b >= (1ll << 31)) {       // (image_segment indexes a segment with 32 bits)
     set_error("weight_image_job: an image of %lld segments", (long long)(j.segs_a > j.segs_b ? j.segs_a : j.segs_b));
     return -1;
@@ -1913,21 +1864,17 @@ extern "C" int lidal_conv_weight_image_batch(const void* jobs, int n_jobs, int64
   if (n_jobs == 0 || total_segments == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   const unsigned grid = (unsigned)cdiv(total_segments, 256);
-#define IMG_BATCH(TI, TO) \
-  weight_image_batch_kernel<TI, TO><<<grid, 256, 0, s>>>((const ImageJob*)jobs, n_jobs, total_segments)
+  bool known = true;
   if (dtype == LIDAL_F32_SPLIT && w_dtype == LIDAL_F32)
     weight_image_batch_split_kernel<float><<<grid, 256, 0, s>>>((const ImageJob*)jobs, n_jobs, total_segments);
   else if (dtype == LIDAL_F32_SPLIT && w_dtype == LIDAL_BF16)
     weight_image_batch_split_kernel<__bf16><<<grid, 256, 0, s>>>((const ImageJob*)jobs, n_jobs, total_segments);
-  else if (w_dtype == LIDAL_F32 && dtype == LIDAL_F32) IMG_BATCH(float, float);
-  else if (w_dtype == LIDAL_F32 && dtype == LIDAL_BF16) IMG_BATCH(float, __bf16);
-  else if (w_dtype == LIDAL_BF16 && dtype == LIDAL_BF16) IMG_BATCH(__bf16, __bf16);
-  else if (w_dtype == LIDAL_BF16 && dtype == LIDAL_F32) IMG_BATCH(__bf16, float);
-  else {
-    set_error("weight_image_batch: bad dtypes %d %d", w_dtype, dtype);
-    return 2;
-  }
-#undef IMG_BATCH
+  else
+    known = with_image_types(w_dtype, dtype, [&](auto* ti, auto* to) {
+      weight_image_batch_kernel<std::remove_pointer_t<decltype(ti)>, std::remove_pointer_t<decltype(to)>>
+          <<<grid, 256, 0, s>>>((const ImageJob*)jobs, n_jobs, total_segments);
+    });
+  LIDAL_REQUIRE(known, "weight_image_batch: bad dtypes %d %d", w_dtype, dtype);
   LIDAL_CHECK_LAUNCH("lidal_conv_weight_image_batch");
   return 0;
 }
@@ -1996,15 +1943,14 @@ extern "C" int lidal_conv_apply_image(const void* in, const void* wimg, const in
                                       int dtype, const float* ep_scale, const float* ep_shift,
                                       int ep_relu, const void* ep_residual, float* tile_stats,
                                       void* stream) {
-  BnBwd none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
   return conv_apply_image(in, wimg, nbr, perm, tile_masks, out, n_in, n_out, ci, co, k, kflip, dtype, ep_scale,
-                          ep_shift, ep_relu, ep_residual, tile_stats, none, nullptr, 0, (hipStream_t)stream);
+                          ep_shift, ep_relu, ep_residual, tile_stats, NO_BNB, nullptr, 0, (hipStream_t)stream);
 }
 
 extern "C" int64_t lidal_conv_apply_workspace_bytes(int64_t n_out, int co) {
   const int64_t tiles = cdiv(n_out > 0 ? n_out : 1, TILE_ROWS);
-  if (tiles * cdiv(co, 128) > SPLIT_F32_MAX_WGS) return 0;    // (no tiling makes few enough workgroups to be split)
-  return 4 * tiles * TILE_ROWS * align_up(co, 128) * 4;
+  if (tiles * cdiv(co, 128) > SPLIT_ANY_MAX_WGS) return 0;    // (no tiling makes few enough workgroups to be split)
+  return SPLIT_MAX_SHARES * tiles * TILE_ROWS * align_up(co, 128) * 4;
 }
 
 extern "C" int lidal_conv_apply_image_ws(const void* in, const void* wimg, const int32_t* nbr,
@@ -2013,9 +1959,8 @@ extern "C" int lidal_conv_apply_image_ws(const void* in, const void* wimg, const
                                          int dtype, const float* ep_scale, const float* ep_shift,
                                          int ep_relu, const void* ep_residual, float* tile_stats, void* ws,
                                          int64_t ws_bytes, void* stream) {
-  BnBwd none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
   return conv_apply_image(in, wimg, nbr, perm, tile_masks, out, n_in, n_out, ci, co, k, kflip, dtype, ep_scale,
-                          ep_shift, ep_relu, ep_residual, tile_stats, none, ws, ws_bytes, (hipStream_t)stream);
+                          ep_shift, ep_relu, ep_residual, tile_stats, NO_BNB, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int lidal_conv_dgrad_bn_sums(const void* gout, const void* wimg, const int32_t* nbr,
